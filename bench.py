@@ -6,6 +6,12 @@
   python bench.py --workload {s1,s2,s3,s4}             (default s1 == BASELINE config 2; the others are extra lines)
   python bench.py --sequences-per-gpu S                (S independent sequences on each GPU, one host thread each, their per-frame
                                                         launches issued together: an instance group; --no-group: S lone instances)
+  python bench.py --full                               (also the legs and studies beyond the headline figure, listed below)
+  python bench.py --dump-outputs DIR                   (what the timed path returned to its caller after the last timed step, as .npy)
+
+A plain run sets up, warms up, times --steps steps and prints the line; the figures that cost extra frames, other runs or
+other processes -- `sustained`, `variants`, `cpu_baseline` / `cpu_baseline_mt`, `device_state` (rocm-smi clock and power
+queries), s3's `precision_study` -- are measured with --full only.
 
 A "step" is one camera frame of one sequence pushed through the whole hot path behind the reference's C API
 (include/XRSLAM.h, the player's call sequence of xrslam-pc/player/src/main.cpp:116-169): ~10 gyro + ~10 accel samples,
@@ -35,7 +41,7 @@ been marginalised (once per sequence through the eigen path: a rank-deficient pr
 the missing frames run as an untimed pre-roll in front of the W warmup steps (config.untimed_preroll_frames) -- the frames it
 skips are cheaper on average (smaller windows), so this never flatters `value` except for that one-off, whose cost the line
 states as `one_off_ms` (the longest pre-roll frame against the pre-roll's median frame).
-Beside `value` the line carries (round 5): `sustained` -- the headline mode itself continued for --sustained-frames more frames of the
+With --full, beside `value` the line carries: `sustained` -- the headline mode itself continued for --sustained-frames more frames of the
 same stream (a --steps 20 line is a 12 ms sample); `variants` -- each leg behind six untimed settle frames, in four timed chunks
 (`chunk_ms`), with its keyframe / solve / BA-iteration counts (legs cover different stretches of the stream: comparable at equal counts);
 `cpu_baseline.ms_per_ba_iteration` / `.ms_per_marginalization` -- the CPU checker's own solve and marginalisation clocks over the same
@@ -237,6 +243,50 @@ def precision_study_full_solve(pd):
     return res
 
 
+def save_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64 (a few kilobytes per sequence)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, np.float64))
+
+
+def session_outputs(sessions, prefix=""):
+    """What a caller of the timed path holds after its last step, through XRSLAMGetResult of every sequence: tracking state
+    (XRSLAMState), body and camera pose (timestamp, translation, quaternion x y z w: the layout of the recorded poses), IMU biases
+    (accelerometer, gyroscope) and the valid landmarks of the window (one array per sequence: their number differs)."""
+    import ctypes as C
+    from xrslam_amd.harness import runner
+    body_pose, camera_pose, state, landmarks, bias = 0, 1, 2, 3, 5      # XRSLAMResultType (include/XRSLAM.h)
+
+    class Landmarks(C.Structure):      # XRSLAMLandmarks
+        _fields_ = [("landmarks", C.POINTER(C.c_double)), ("num_landmarks", C.c_int)]
+
+    class Bias(C.Structure):           # XRSLAMIMUBias
+        _fields_ = [("acc", C.c_double * 3), ("gyr", C.c_double * 3)]
+
+    def pose(s, kind):
+        p = runner.XRSLAMPose()
+        s.api.get_result(kind, C.byref(p))
+        return [p.timestamp] + list(p.translation) + list(p.quaternion)
+
+    rows = {"tracking_state": [], "body_pose": [], "camera_pose": [], "imu_bias": []}
+    out = {}
+    for i, s in enumerate(sessions):
+        st, b, lm = C.c_int(-1), Bias(), Landmarks()
+        s.api.get_result(state, C.byref(st))
+        s.api.get_result(bias, C.byref(b))
+        s.api.get_result(landmarks, C.byref(lm))     # the array is the caller's, as in the reference; the library exports no free
+        rows["tracking_state"].append(st.value)
+        rows["body_pose"].append(pose(s, body_pose))
+        rows["camera_pose"].append(pose(s, camera_pose))
+        rows["imu_bias"].append(list(b.acc) + list(b.gyr))
+        n = max(0, lm.num_landmarks)
+        out["%slandmarks_seq%d" % (prefix, i)] = (np.ctypeslib.as_array(lm.landmarks, shape=(n * 3,)).reshape(n, 3).copy()
+                                                  if n else np.zeros((0, 3)))
+    out.update({prefix + k: np.array(v, np.float64) for k, v in rows.items()})
+    return out
+
+
 def bench_s4(args, out_common):
     """S4: frozen refine_window problems replayed through the C ABI of plug point #2."""
     from xrslam_amd import ba
@@ -252,7 +302,8 @@ def bench_s4(args, out_common):
             ctx.solve(pd.copy())
         it, ms = 0, 0.0
         for _ in range(reps):
-            sm = ctx.solve(pd.copy())     # a solve works in place: every repetition starts from the frozen states
+            last = pd.copy()
+            sm = ctx.solve(last)          # a solve works in place: every repetition starts from the frozen states
             it += sm.iterations
             ms += sm.ms_solve             # wall clock of the whole xrhip_ba_solve call (staging, kernels, read-back), taken
         dt = 1e-3 * ms                    # inside the library: the interpreter's copy / marshalling is not in it
@@ -268,6 +319,11 @@ def bench_s4(args, out_common):
                 "ms_per_ba_iteration": round(sum(p["ms_per_ba_iteration"] * p["iterations_per_solve"] for p in per) /
                                              max(1e-9, sum(p["iterations_per_solve"] for p in per)), 5),
                 "snapshots": per})
+    if args.dump_outputs:
+        # the last timed step: the last snapshot's last solve -- its states, solved in place, and its summary
+        save_outputs(args.dump_outputs, {"ba_frame_state": last.frame_state, "ba_inv_depth": last.inv_depth,
+                                         "ba_summary": [sm.iterations, sm.successful_steps, sm.termination, sm.usable,
+                                                        sm.initial_cost, sm.final_cost]})
     print(json.dumps(out))
 
 
@@ -318,14 +374,14 @@ def main():
                     help="with --sequences-per-gpu S: S lone instances (every sequence launches for itself, round 3's form) instead of "
                          "one instance group whose members share launches (XRSLAMAmdGroup)")
     ap.add_argument("--cpu-frames", type=int, default=240,
-                    help="most frames of the bounded CPU-reference sample (0 = skip); the first 40 are its warm-up")
+                    help="with --full: most frames of the bounded CPU-reference sample (0 = skip); the first 40 are its warm-up")
     ap.add_argument("--cpu-seconds", type=float, default=20.0,
                     help="time budget of each CPU-reference leg: the sample stops at --cpu-frames or here, whichever comes first")
     ap.add_argument("--variant-frames", type=int, default=100,
-                    help="frames of each extra leg on the same stream after the timed region -- resident / pipelined / "
+                    help="with --full: frames of each extra leg on the same stream after the timed region -- resident / pipelined / "
                          "pipelined_resident (0 = skip; one sequence on one GPU only)")
     ap.add_argument("--sustained-frames", type=int, default=150,
-                    help="frames of the `sustained` leg: the HEADLINE mode itself continued on the same stream right after the timed "
+                    help="with --full: frames of the `sustained` leg: the HEADLINE mode itself continued on the same stream right after the timed "
                          "region (a --steps 20 line is a 12 ms sample; this is the same call over a longer one; 0 = skip; one "
                          "sequence on one GPU only)")
     ap.add_argument("--image", default="host", choices=["host", "resident"],
@@ -348,6 +404,13 @@ def main():
                          "DIR/poses_rank<R>_seq<I>.npy -- tests compare them with solo runs of the same streams")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="exercise only the launcher / process-group path (no device needed, prints no measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the sustained and variant legs (--sustained-frames, "
+                         "--variant-frames), the CPU-reference baseline (--cpu-frames), the device's clock / power state and, "
+                         "with --workload s3, the fp32 / bf16 precision study")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned to its caller in its last step as DIR/<name>.npy "
+                         "(float64; with the same arguments the inputs are the same in every run)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0 or args.sequences_per_gpu < 1 or args.gpus < 1:
         raise SystemExit("--gpus and --steps must be >= 1, --warmup >= 0, --sequences-per-gpu >= 1")
@@ -380,8 +443,8 @@ def main():
         # the missing frames as an untimed pre-roll (module docstring)
         preroll = max(0, 4 * wl["window"] + 16 - args.warmup)
         slam_yaml, sensor_yaml = os.path.join(CFG, wl["slam"]), os.path.join(CFG, wl["sensor"])
-        variant_frames = args.variant_frames if (S == 1 and world == 1) else 0
-        sustained_frames = args.sustained_frames if (S == 1 and world == 1) else 0
+        variant_frames = args.variant_frames if (args.full and S == 1 and world == 1) else 0
+        sustained_frames = args.sustained_frames if (args.full and S == 1 and world == 1) else 0
         n_frames = preroll + args.warmup + args.steps + sustained_frames + 3 * (variant_frames + (LEG_SETTLE if variant_frames else 0))
         if args.euroc:
             from xrslam_amd.harness import euroc
@@ -423,7 +486,7 @@ def main():
     _lib.set_device(device_index)
     kernel_rev = _lib.kernel_revision()
     peaks, traffic, traffic_note = roofline_extras(kernel_rev, args.workload)
-    power0 = device_power_state(device_index)
+    power0 = device_power_state(device_index) if args.full else {}
     common = {"n_gpus": world, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "kernel_rev": kernel_rev}
 
     if args.workload == "s4":
@@ -440,8 +503,9 @@ def main():
     native = not args.python_loop or S > 1
     sessions, keep = [], []
     igroup = runner.Group(_lib.LIB_PATH) if (S > 1 and not args.no_group) else None
+    upload = resident or variant_frames > 0
     for seq in seqs:
-        dev = torch.from_numpy(seq["frames"]).cuda()     # the `resident` legs read their frames from here
+        dev = torch.from_numpy(seq["frames"]).cuda() if upload else None     # the `resident` legs read their frames from here
         keep.append(dev)
         h, w = seq["frames"].shape[1:]
         sessions.append(runner.Session(_lib.LIB_PATH, seq, slam_yaml=slam_yaml, sensor_yaml=sensor_yaml,
@@ -450,7 +514,7 @@ def main():
                                        device_undistort="cv_undistort" if real is not None else None, group=igroup))
     torch.cuda.synchronize()
     sess, seq = sessions[0], sessions[0].seq
-    dev_frames0 = (keep[0].data_ptr(), seq["frames"].shape[1] * seq["frames"].shape[2], seq["frames"].shape[2])
+    dev_frames0 = (keep[0].data_ptr(), seq["frames"].shape[1] * seq["frames"].shape[2], seq["frames"].shape[2]) if upload else None
 
     def barrier():
         group.barrier()
@@ -532,6 +596,8 @@ def main():
     for s in sessions:
         s.set_profiling(False)
     my_elapsed = elapsed
+    if args.dump_outputs:
+        save_outputs(args.dump_outputs, session_outputs(sessions, "rank%d_" % rank if world > 1 else ""))
     if args.dump_poses:
         os.makedirs(args.dump_poses, exist_ok=True)
         for i, s in enumerate(sessions):
@@ -539,7 +605,7 @@ def main():
     red = group.reduce_metrics(args.steps * S, elapsed)      # frames: SUM, wall seconds: MAX over ranks
     elapsed, total_frames = red["seconds"], red["frames"]
     # per-rank diagnostics into rank 0's line: a slow rank (clocked-down device, a device shared by two ranks) is visible there
-    power1 = device_power_state(device_index)
+    power1 = device_power_state(device_index) if args.full else {}
     rows = group.gather_rows([rank, device_index, args.steps * S / my_elapsed, my_elapsed, power1.get("sclk_mhz", -1.0),
                               power1.get("mclk_mhz", -1.0), power1.get("power_cap_w", -1.0), power1.get("power_w", -1.0),
                               float(int(kernel_rev, 16)) if all(ch in "0123456789abcdef" for ch in kernel_rev) else -1.0])
@@ -667,12 +733,13 @@ def main():
                                                           "scope": "tracker stage of %d sequence(s) on this GPU; timed wall clock" % S})(
                 sum(args.steps * (3.0 * px + (pyr - px / 64.0) + (pyr - px) + 5.0 * pyr + 5.0 * px) + 2420.0 * k.lk_templates + 484.0 * k.lk_iterations
                     for k in all_klt)))(float(wl["w"] * wl["h"]), float(sum(((wl["w"] + (1 << l) - 1) >> l) * ((wl["h"] + (1 << l) - 1) >> l) for l in range(4)))),
-            # what every rank measured on its own clock, and the clock / power state of its device right after the timed region
+            # what every rank measured on its own clock, and (--full) the clock / power state of its device right after the timed region
             "per_rank": [{"rank": int(r[0]), "device": int(r[1]), "frames_per_s": round(r[2], 3), "seconds": round(r[3], 4),
                           "sclk_mhz": r[4] if r[4] >= 0 else None, "mclk_mhz": r[5] if r[5] >= 0 else None,
                           "power_cap_w": r[6] if r[6] >= 0 else None, "power_w": r[7] if r[7] >= 0 else None} for r in rows],
-            "device_state": {"before": power0, "after_timed_region": power1},
         })
+        if args.full:
+            out["device_state"] = {"before": power0, "after_timed_region": power1}
         if gstats is not None:
             # the instance group: requests per batch = sequences one launch served; ms = HIP events around a batch's kernels
             out["group"] = {k: dict(v, requests_per_batch=round(v["requests"] / max(1, v["batches"]), 2),
@@ -693,7 +760,7 @@ def main():
             ts = sorted(step_ms[:args.steps])
             out["step_ms"] = {"median": round(ts[len(ts) // 2], 4), "longest": [round(v, 3) for v in ts[-5:]],
                               "at": [int(i) for i in sorted(range(len(step_ms[:args.steps])), key=lambda i: step_ms[i])[-5:]]}
-        if args.workload == "s3":
+        if args.workload == "s3" and args.full:
             try:
                 out["precision_study"] = precision_study()
             except Exception as e:   # noqa: BLE001  (a study, not the measurement)
@@ -786,7 +853,7 @@ def main():
                            "hand-offs (a different, reproducible trajectory: the backend is one frame late)")
             out["variants"] = var
             sess.api.set_threading(1 if pipelined else 0)
-        if args.cpu_frames > 40 and world == 1 and S == 1 and real is None:
+        if args.full and args.cpu_frames > 40 and world == 1 and S == 1 and real is None:
             import subprocess
             ref_lib = os.path.join(ROOT, "oracle", "_build", "libxrslam_oracle.so")
             if not os.path.exists(ref_lib):

@@ -81,7 +81,8 @@ def test_slam_keys_are_optional(lib, tmp_path):
     lib.XRSLAMDestroy()
 
 
-REF_CFG = "/root/reference/configs"
+# the reference's configs/euroc_slam.yaml and configs/euroc_sensor.yaml, byte for byte (data fixtures)
+REF_CFG = os.path.join(ROOT, "tests", "golden", "reference_configs")
 
 
 def _describe(lib, slam, sensor):
@@ -101,9 +102,8 @@ def _describe(lib, slam, sensor):
     return dict(ln.split(" = ") for ln in text.splitlines()), bytes(cam)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_CFG, "euroc_slam.yaml")), reason="the reference tree is not on this box")
 def test_the_reference_yaml_files_load_verbatim_and_mean_the_shipped_configuration(lib):
-    """XRSLAMCreate on /root/reference/configs/euroc_slam.yaml + euroc_sensor.yaml AS SHIPPED BY THE REFERENCE (multi-line flow
+    """XRSLAMCreate on the reference's configs/euroc_slam.yaml + euroc_sensor.yaml AS SHIPPED BY THE REFERENCE (multi-line flow
     sequences, the nested T_BS map, keys this library does not read): accepted, and every value it resolves to -- all of
     xrslam::Config's accessors (XRSLAMAmdDescribeConfig) and the XRSLAMAmdCameraConfig the dataset readers ask for -- equals what
     the repo's re-formatted copies under configs/ resolve to."""

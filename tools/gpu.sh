@@ -4,7 +4,7 @@
 #   gpurun --timeout 1500 -- tools/gpu.sh TAG step [step ...]
 # steps (NAME or NAME:ARGS; ARGS are passed on verbatim):
 #   tests[:pytest args]     the GPU suite (default: tests)              smoke              __graft_entry__.smoke()
-#   bench[:bench.py args]   one bench.py line + a one-line digest       driver             the driver's --steps 20 --warmup 5 line
+#   bench[:bench.py args]   one bench.py --full line + a digest          driver             the driver's --steps 20 --warmup 5 line
 #   multi:S [args]          bench.py --sequences-per-gpu S              procs:N Q [S]      N processes on this GPU (gloo), Q HW queues each, S grouped sequences in each
 #   rccl1                   RunGroup's collectives over nccl (= RCCL) with one rank (tools/check_rccl.py)
 #   trace[:bench.py args]   rocprofv3 --kernel-trace --stats + per-kernel averages         pmc[:args]   MFMA / FETCH_SIZE / WRITE_SIZE passes
@@ -50,7 +50,7 @@ for step in "$@"; do
   case "$name" in
     tests)  timeout 1500 python -m pytest ${arg:-tests} -m gpu -x -q > "$O/tests_${TAG}_$n.log" 2>&1; tail -3 "$O/tests_${TAG}_$n.log" ;;
     smoke)  timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke_$TAG.log" 2>&1; tail -2 "$O/smoke_$TAG.log" ;;
-    bench)  timeout 500 python bench.py $arg > "$O/bench_${TAG}_$n.json" 2> "$O/bench_${TAG}_$n.err"; digest "$O/bench_${TAG}_$n.json"; tail -2 "$O/bench_${TAG}_$n.err" ;;
+    bench)  timeout 600 python bench.py --full $arg > "$O/bench_${TAG}_$n.json" 2> "$O/bench_${TAG}_$n.err"; digest "$O/bench_${TAG}_$n.json"; tail -2 "$O/bench_${TAG}_$n.err" ;;
     driver) timeout 240 python bench.py --steps 20 --warmup 5 > "$O/bench_${TAG}_driver.json" 2> "$O/bench_${TAG}_driver.err"; digest "$O/bench_${TAG}_driver.json" ;;
     multi)  set -- $arg; S="$1"; shift; ENVS=""; ARGS=""   # multi:S [VAR=VALUE ...] [bench.py args]
             for t in "$@"; do case "$t" in -*) ARGS="$ARGS $t" ;; *=*) ENVS="$ENVS $t" ;; *) ARGS="$ARGS $t" ;; esac; done

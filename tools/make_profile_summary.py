@@ -4,7 +4,7 @@ On the GPU box (one gpurun call; PMC passes are separate runs without any other 
     cd /tmp && export TMPDIR=/tmp
     rocprofv3 --kernel-trace --memory-copy-trace --stats -d $R/gpurun_out/prof_TAG -o full -- python $R/bench.py --steps 100 --warmup 40 --cpu-frames 0 --no-profile
     for C in FETCH_SIZE WRITE_SIZE; do rocprofv3 --pmc $C --kernel-trace --output-format csv -d $R/gpurun_out/pmc_TAG/$C -o pmc -- python $R/bench.py --steps 60 --warmup 40 --cpu-frames 0 --no-profile; done
-    python $R/bench.py > $R/gpurun_out/bench_TAG.json
+    python $R/bench.py --full > <the same output folder>/bench_TAG.json
 (tools/gpu.sh TAG tests bench trace peaks pmc is that command sequence.)  Here:
     python tools/make_profile_summary.py TAG v13 "one-line description of this version"
 XR_ROUND (default r01) is the prefix of the files written under profiles/ (r02 in round 2, ...); the PMC header text is
