@@ -1,0 +1,171 @@
+"""Oracle parity of xrhip_ba_solve on every size route it can take, on both sides of every boundary between them.
+
+xrhip_ba_solve picks its code path from the problem's size (csrc/ba_api.hip).  Each case below builds a problem just inside or just
+outside one of these decisions, asserts -- through xrhip_ba_debug_last_route -- the route the solve actually took (a later change of
+a threshold or of the LDS limit must not quietly move a case to the route next door), and holds the result to the oracle with the
+criteria of tests/ba_parity.py.  Where a route admits a prior factor, it is run once with and once without one.
+
+  decision                          source (csrc/)                         boundary
+  chain()                           ba_api.hip chain(), ba_chain.hip.h     no free landmark, no prior, nffp = 0, na <= 90,
+                                                                           <= 6 free frames, NI <= 8, M + MR <= 1024, and
+                                                                           chain_layout() within the 150 KiB of LDS
+  tiny() / small_mid()              ba_api.hip tiny(), small_mid()         no free landmark, na <= 16; kb_tiny also M + MR <= 640
+  kb_solve_try<256> vs <512>        ba_api.hip solve_try_threads()         M + MR <= 640 and na <= 64 (and not wide_first)
+  solve_lds: use_lds 2 / 1 / 0      ba_api.hip solve_lds()                 150 KiB of LDS: tiled up to na = 165, packed at 180,
+                                                                           in the global buffer (tiled, in place) from 195
+  tile grid of the tiled layout     dense_lds.hip.h tl_tile_rows(na + 1)   na = 255: the rhs row is the last row of the grid
+  rhs gather of the in-place layout ba_kernels.hip.h factor_stage_tiled    na > 512: more unknowns than kb_solve_try's threads
+  wide_trials()                     ba_api.hip wide_trials()               M >= 256 and F <= 32
+  wide_first()                      ba_api.hip wide_first()                wide_trials, M >= 600 and na >= 90
+"""
+import numpy as np
+import pytest
+
+from tests import ba_synth as bs
+from tests.ba_parity import solve_both
+from xrslam_amd import abi
+
+pytestmark = pytest.mark.gpu
+
+HELD = abi.FIX_POSE | abi.FIX_MOTION
+
+
+def _free_prior(states, frames, seed):
+    """A prior on `frames` linearised a little away from their states: diagonal sqrt-information (0.01 rad / 1 cm on the pose,
+    0.1 m/s and the biases' random walk on the motion), infovec zero."""
+    rng = np.random.RandomState(seed)
+    n = 15 * len(frames)
+    w = np.tile(np.concatenate([np.full(6, 100.0), np.full(3, 10.0), np.full(3, 1e3), np.full(3, 1e2)]), len(frames))
+    lin = states[frames].copy()
+    lin[:, 4:7] += 1e-3 * rng.randn(len(frames), 3)
+    return dict(frames=np.asarray(frames), sqrt_info=np.diag(w), infovec=np.zeros(n), lin=lin)
+
+
+def window(K, L, seed, prior, fixed=0):
+    """refine_window-shaped: free landmarks (a Schur complement), all frames free but the first `fixed`; with the window's gauge
+    prior (ba_synth.make_window) or without a prior.  na = 15 (K - fixed)."""
+    return bs.make_window(K=K, L=L, seed=seed, with_prior=prior, n_fixed_first=fixed)[0]
+
+
+def one_free(K, L, seed, prior, all_imu=False):
+    """localize_newframe-shaped: only the last frame free, every landmark held, the reprojection factors into the last frame.
+    all_imu: keep all K - 1 IMU factors (NI > 8 rules out kb_chain without a prior).  na = 15."""
+    pd, truth = bs.make_window(K=K, L=L, seed=seed, with_prior=False)
+    j = K - 1
+    fix = np.full(K, HELD, np.uint8)
+    fix[j] = 0
+    keep = pd.obs_tgt == j
+    obs = dict(tgt=pd.obs_tgt[keep], ref=pd.obs_ref[keep], lm=pd.obs_lm[keep], z_tgt=pd.obs_z_tgt[keep], z_ref=pd.obs_z_ref[keep])
+    states = truth["states"].copy()
+    states[j] = pd.frame_state[j]
+    ki = np.arange(len(pd.imu_j)) if all_imu else np.where(pd.imu_j == j)[0]
+    imu = dict(i=pd.imu_i[ki], j=pd.imu_j[ki], data=pd.imu_data[ki])
+    pr = _free_prior(states, [j], seed) if prior else None
+    return abi.BaProblemData(states, fix, bs.CAM_EXT, bs.IMU_EXT, bs.SQRT_INV_COV, truth["inv_depth"], np.ones(L, np.uint8),
+                             obs=obs, imu=imu, prior=pr, max_iterations=30)
+
+
+def subwindow(K, L, seed, prior, first_imu=True):
+    """refine_subwindow-shaped: frame 0 held, frames 1 .. K-1 free, every landmark held, only the reprojection factors of the
+    landmarks frame 0 anchors (no factor between two free poses).  first_imu=False drops the IMU factor 0 -> 1.  na = 15 (K - 1)."""
+    pd, _ = bs.make_window(K=K, L=L, seed=seed, with_prior=False, n_fixed_first=1)
+    keep = pd.obs_ref == 0
+    obs = dict(tgt=pd.obs_tgt[keep], ref=pd.obs_ref[keep], lm=pd.obs_lm[keep], z_tgt=pd.obs_z_tgt[keep], z_ref=pd.obs_z_ref[keep])
+    ki = (pd.imu_i >= 0) if first_imu else (pd.imu_i > 0)
+    imu = dict(i=pd.imu_i[ki], j=pd.imu_j[ki], data=pd.imu_data[ki])
+    pr = _free_prior(pd.frame_state, list(range(1, K)), seed) if prior else None
+    return abi.BaProblemData(pd.frame_state, pd.frame_fix, bs.CAM_EXT, bs.IMU_EXT, bs.SQRT_INV_COV, pd.inv_depth,
+                             np.ones(L, np.uint8), obs=obs, imu=imu, prior=pr, max_iterations=30)
+
+
+def dims(pd):
+    """The sizes the route decisions read: M (reprojection factors), NI, NP, na, F."""
+    free = [(f & abi.FIX_POSE) == 0 for f in pd.frame_fix], [(f & abi.FIX_MOTION) == 0 for f in pd.frame_fix]
+    na = 6 * sum(free[0]) + 9 * sum(free[1])
+    return dict(M=len(pd.obs_tgt), NI=len(pd.imu_i), NP=len(pd.prior_frames), na=na, F=len(pd.frame_state))
+
+
+def route(kind, use_lds=2, block=512, wt=0, wf=0):
+    """What xrhip_ba_debug_last_route should report (na and F are checked against the problem)."""
+    multi = kind in ("small_mid", "multi")
+    return dict(route=kind, use_lds=-1 if kind == "chain" else use_lds, sred_tiled=int(multi and use_lds == 0),
+                block=block if multi else 0, wide_trials=wt, wide_first=wf)
+
+
+# id: (problem, expected route, state rtol).  M = reprojection factors, NI = IMU factors, na = free frame dofs, F = frames.
+CASES = {
+    # kb_tiny (M <= 640) vs kb_small_mid (M > 640): a prior, or NI = 9 > 8, keeps kb_chain out
+    "tiny_prior_M639": (lambda: one_free(4, 750, 3, True), route("tiny"), 1e-7),
+    "tiny_imu9_M618": (lambda: one_free(10, 700, 3, False, all_imu=True), route("tiny"), 1e-7),
+    "small_mid_prior_M682": (lambda: one_free(4, 800, 3, True), route("small_mid", wt=1), 1e-7),
+    "small_mid_imu9_M709": (lambda: one_free(10, 800, 3, False, all_imu=True), route("small_mid", wt=1), 1e-7),
+    "chain_one_free_M682": (lambda: one_free(4, 800, 3, False), route("chain"), 1e-7),
+    # kb_chain at 6 free frames and <= 1024 factors vs a prior, 7 free frames, > 1024 factors.  Its LDS layout (chain_layout) must
+    # fit 150 KiB as well: at na = 90 that holds with five IMU factors (147 KiB at M = 977) but not with six (154 KiB)
+    "chain_free6_NI5_M977": (lambda: subwindow(7, 240, 5, False, first_imu=False), route("chain"), 1e-7),
+    "multi_free6_NI6_M977": (lambda: subwindow(7, 240, 5, False), route("multi", wt=1, wf=1), 1e-7),
+    "multi_free6_prior_M977": (lambda: subwindow(7, 240, 5, True, first_imu=False), route("multi", wt=1, wf=1), 1e-7),
+    "multi_free6_NI5_M1246": (lambda: subwindow(7, 300, 5, False, first_imu=False), route("multi", wt=1, wf=1), 1e-7),
+    "multi_free7_M975": (lambda: subwindow(8, 200, 5, False), route("multi", wt=1, wf=1), 1e-7),
+    "multi_free7_prior_M975": (lambda: subwindow(8, 200, 5, True), route("multi", wt=1, wf=1), 1e-7),
+    # kb_solve_try<256> (na <= 64, M <= 640) vs <512>
+    # (with the gauge prior and all four frames free the trust region stalls -- 30 iterations, 6 accepted -- and the final costs of
+    # that walk part at 1.1e-8: frame 0 is held instead)
+    "na60_prior": (lambda: window(5, 100, 7, True, fixed=1), route("multi", block=256, wt=1), 1e-7),
+    "na60": (lambda: window(5, 100, 7, False, fixed=1), route("multi", block=256, wt=1), 1e-7),
+    "na75_prior": (lambda: window(5, 100, 7, True), route("multi", wt=1), 1e-7),
+    "na75": (lambda: window(6, 100, 7, False, fixed=1), route("multi", wt=1), 1e-7),
+    # wide_first (M >= 600 and na >= 90) vs wide_trials only
+    "na75_M600_prior": (lambda: window(5, 200, 9, True), route("multi", wt=1), 1e-7),
+    "na90_prior": (lambda: window(6, 100, 9, True), route("multi", wt=1), 1e-7),
+    "na90_M600_prior": (lambda: window(6, 200, 9, True), route("multi", wt=1, wf=1), 1e-7),
+    "na90_M600": (lambda: window(7, 200, 9, False, fixed=1), route("multi", wt=1, wf=1), 1e-7),
+    # solve_lds: tiled in LDS up to 165 unknowns, packed triangle in LDS at 180, factored in place in the global buffer from 195;
+    # at na = 255 the rhs row is the last row of the tile grid
+    "na165_prior": (lambda: window(11, 150, 2, True), route("multi", wt=1, wf=1), 1e-7),
+    "na165": (lambda: window(12, 150, 2, False, fixed=1), route("multi", wt=1, wf=1), 1e-7),
+    "na180_prior": (lambda: window(12, 150, 4, True), route("multi", use_lds=1, wt=1, wf=1), 1e-7),
+    "na180": (lambda: window(13, 150, 4, False, fixed=1), route("multi", use_lds=1, wt=1, wf=1), 1e-7),
+    "na195_prior": (lambda: window(13, 150, 6, True), route("multi", use_lds=0, wt=1, wf=1), 1e-7),
+    "na195": (lambda: window(14, 150, 6, False, fixed=1), route("multi", use_lds=0, wt=1, wf=1), 1e-7),
+    "na240_prior": (lambda: window(16, 150, 8, True), route("multi", use_lds=0, wt=1, wf=1), 1e-7),
+    "na240": (lambda: window(17, 150, 8, False, fixed=1), route("multi", use_lds=0, wt=1, wf=1), 1e-7),
+    "na255_prior": (lambda: window(17, 150, 10, True), route("multi", use_lds=0, wt=1, wf=1), 1e-7),
+    "na255": (lambda: window(18, 150, 10, False, fixed=1), route("multi", use_lds=0, wt=1, wf=1), 1e-7),
+    # wide_trials needs F <= 32: a 33-frame window costs its trials inside kb_solve_try
+    "F32_prior": (lambda: window(32, 40, 9, True), route("multi", use_lds=0, wt=1, wf=1), 1e-7),
+    "F32": (lambda: window(32, 40, 9, False, fixed=1), route("multi", use_lds=0, wt=1, wf=1), 1e-7),
+    "F32_M_below_600_prior": (lambda: window(32, 25, 9, True), route("multi", use_lds=0, wt=1), 1e-7),
+    "F33_prior": (lambda: window(33, 40, 9, True), route("multi", use_lds=0), 1e-7),
+    "F33": (lambda: window(33, 40, 9, False, fixed=1), route("multi", use_lds=0), 1e-7),
+    # past one kb_solve_try thread per unknown (512)
+    "na510_prior": (lambda: window(34, 40, 11, True), route("multi", use_lds=0), 1e-7),
+    "na510": (lambda: window(35, 40, 11, False, fixed=1), route("multi", use_lds=0), 1e-7),
+    "na525_prior": (lambda: window(35, 40, 12, True), route("multi", use_lds=0), 1e-7),
+    "na525": (lambda: window(36, 40, 12, False, fixed=1), route("multi", use_lds=0), 1e-7),
+    "na600_prior": (lambda: window(40, 40, 13, True), route("multi", use_lds=0), 1e-7),
+    "na600": (lambda: window(41, 40, 13, False, fixed=1), route("multi", use_lds=0), 1e-7),
+}
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    from xrslam_amd import ba
+    return ba.BaContext()
+
+
+@pytest.fixture(scope="module")
+def bo():
+    from oracle import ba_oracle
+    return ba_oracle
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_solve_route_parity(ctx, bo, case):
+    make, expect, rtol = CASES[case]
+    pd = make()
+    d = dims(pd)
+    solve_both(ctx, bo, pd, "route_" + case, rtol=rtol)
+    got = ctx.debug_last_route()
+    assert (got["na"], got["F"]) == (d["na"], d["F"]), (case, got, d)
+    assert {k: got[k] for k in expect} == expect, (case, got)

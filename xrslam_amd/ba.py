@@ -51,6 +51,8 @@ def configure(lib):
         lib.xrhip_ba_debug_schur.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     if hasattr(lib, "xrhip_ba_debug_set_schur_precision"):
         lib.xrhip_ba_debug_set_schur_precision.argtypes = [vp, C.c_int]
+    if hasattr(lib, "xrhip_ba_debug_last_route"):
+        lib.xrhip_ba_debug_last_route.argtypes = [vp, vp]
     return lib
 
 
@@ -243,6 +245,18 @@ class BaContext:
         cost = C.c_double()
         check(self._lib.xrhip_ba_debug_linearize(self._h, C.byref(s), _p(H), _p(g), _p(hll), _p(gl), _p(W), C.byref(cost)))
         return dict(H=H, g=g, hll=hll[:Ln], gl=gl[:Ln], W=W[:Ln], cost=cost.value)
+
+    ROUTES = {0: "none", 1: "tiny", 2: "chain", 3: "small_mid", 4: "multi"}
+
+    def debug_last_route(self):
+        """The route the last solve() on this context took (xrhip_ba_debug_last_route): dict with route ("none", "tiny", "chain",
+        "small_mid" = multi-launch with kb_small_mid, "multi"), use_lds (2 / 1 / 0, -1: not used), sred_tiled, block (kb_solve_try's
+        workgroup size, 0: not launched), wide_trials, wide_first, na, F."""
+        out = np.zeros(8, np.int32)
+        check(self._lib.xrhip_ba_debug_last_route(self._h, _p(out)))
+        v = [int(x) for x in out]
+        return dict(route=self.ROUTES[v[0]], use_lds=v[1], sred_tiled=v[2], block=v[3], wide_trials=v[4], wide_first=v[5], na=v[6],
+                    F=v[7])
 
     def set_schur_precision(self, mode):
         """Study aid (BASELINE config 5): 0 = f64 (product), 1 = f32, 2 = bf16 operands in the Schur contraction of the solves that follow."""

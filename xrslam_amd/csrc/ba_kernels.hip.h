@@ -1267,14 +1267,15 @@ __device__ __forceinline__ void solve_block(const BaDims &d, const BaPtrs &p, in
         const int n_tiles = T * (T + 1) / 2;
         const double *src = p.Sred;
         KPROF(0);
-        // the right-hand side row sp (gp - W^T (omega gl)): its two-level gathers are issued first and parked in a register
-        double rhs_v = 0.0;
-        if (tid < na) {
-            const int a = p.act_idx[tid];
+        // the right-hand side row sp (gp - W^T (omega gl)): its two-level gathers are issued first and parked in a register -- the
+        // first pass of a strided loop (na > nt: the in-place layout from 513 unknowns gathers the rest after the tiles)
+        auto rhs_at = [&](int i) __attribute__((always_inline)) -> double {
+            const int a = p.act_idx[i];
             const int fa = a / 15, ka = a - 15 * fa;
             const double sacc = (d.nla && ka < 6) ? wog_at(d, p, 6 * fa + ka) : 0.0;
-            rhs_v = (p.gp[a] - sacc) * p.sp[a];
-        }
+            return (p.gp[a] - sacc) * p.sp[a];
+        };
+        const double rhs_v = tid < na ? rhs_at(tid) : 0.0;
         constexpr int TU = 3;   // tiles (4 loads each) in flight per wavefront; loads are unconditional (clamped), selected afterwards
         for (int t0 = wave; t0 < (in_place ? 0 : n_tiles); t0 += TU * nw) {
             double v[TU][4];
@@ -1303,6 +1304,7 @@ __device__ __forceinline__ void solve_block(const BaDims &d, const BaPtrs &p, in
         }
         __syncthreads();
         if (tid < na) A[tl_idx(na, tid)] = rhs_v;
+        for (int i = tid + nt; i < na; i += nt) A[tl_idx(na, i)] = rhs_at(i);
         __syncthreads();
         KPROF(1);
 #ifdef XRHIP_KPROF
