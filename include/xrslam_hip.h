@@ -413,8 +413,8 @@ int xrhip_ba_debug_marg_guard(xrhip_ba *ctx, double *lambda_bound, int *status8)
 /* study aid (BASELINE.json config 5, "fp32 vs bf16 BA solve"): mode 1 / 2 run the Schur contraction of the following solves on this
  * context with f32 / bf16 matrix-core operands; mode 0 (the default, and what the product always uses) is f64. */
 int xrhip_ba_debug_set_schur_precision(xrhip_ba *ctx, int mode);
-/* test aid: the route the LAST xrhip_ba_solve / xrhip_ba_solve_overlapped on this context took, as the host decided it (no device
- * work).  out8: [0] 0 = nothing free (no launch), 1 = kb_tiny, 2 = kb_chain, 3 = multi-launch with kb_small_mid, 4 = multi-launch;
+/* test aid: the plan the LAST solve on this context was launched from -- xrhip_ba_solve / _overlapped, and a solve queued through
+ * xrhip_ba_solve_begin / _linked / _chained (always [0] = 2 there) -- as the host decided it (no device work).  out8: [0] 0 = nothing free (no launch), 1 = kb_tiny, 2 = kb_chain, 3 = multi-launch with kb_small_mid, 4 = multi-launch;
  * [1] reduced-system layout of kb_tiny / kb_solve_try: 2 = tiled in LDS, 1 = packed triangle in LDS, 0 = global buffer (-1: not
  * used); [2] BaDims::sred_tiled (global buffer factored in place, tiled); [3] workgroup size of kb_solve_try, 256 or 512 (0: not
  * launched); [4] wide_trials (rejected trials on kb_trials_wide); [5] wide_first (the first trial too); [6] na (free frame dofs);

@@ -583,6 +583,7 @@ def test_chained_solves_equal_one_after_the_other(ctx):
         with pytest.raises(Exception):
             ctx2.solve(loc.copy())
         mb = ctx2.solve_end()
+        assert ctx2.debug_last_route()["route"] == "chain"
         np.testing.assert_array_equal(a.frame_state, b.frame_state)
         assert (ma.iterations, ma.final_cost) == (mb.iterations, mb.final_cost)
         assert ctx2.solve_begin(win.copy()) is False

@@ -1,22 +1,23 @@
 """Oracle parity of xrhip_ba_solve on every size route it can take, on both sides of every boundary between them.
 
-xrhip_ba_solve picks its code path from the problem's size (csrc/ba_api.hip).  Each case below builds a problem just inside or just
-outside one of these decisions, asserts -- through xrhip_ba_debug_last_route -- the route the solve actually took (a later change of
-a threshold or of the LDS limit must not quietly move a case to the route next door), and holds the result to the oracle with the
-criteria of tests/ba_parity.py.  Where a route admits a prior factor, it is run once with and once without one.
+xrhip_ba_solve picks its code path from the problem's size, once per solve (csrc/ba_plan.hpp: plan_solve).  Each case below builds a
+problem just inside or just outside one of these decisions, asserts -- through xrhip_ba_debug_last_route, which reports the plan the
+solve was launched from -- the route the solve actually took (a later change of a threshold or of the LDS limit must not quietly move
+a case to the route next door), and holds the result to the oracle with the criteria of tests/ba_parity.py.  Where a route admits a
+prior factor, it is run once with and once without one.  (tests/test_ba_plan_host.py pins the same boundaries on bare sizes, no GPU.)
 
-  decision                          source (csrc/)                         boundary
-  chain()                           ba_api.hip chain(), ba_chain.hip.h     no free landmark, no prior, nffp = 0, na <= 90,
+  decision (SolvePlan)              source (csrc/)                         boundary
+  route = chain, chain_lds          ba_plan.hpp plan_solve, ba_chain.hip.h no free landmark, no prior, nffp = 0, na <= 90,
                                                                            <= 6 free frames, NI <= 8, M + MR <= 1024, and
                                                                            chain_layout() within the 150 KiB of LDS
-  tiny() / small_mid()              ba_api.hip tiny(), small_mid()         no free landmark, na <= 16; kb_tiny also M + MR <= 640
-  kb_solve_try<256> vs <512>        ba_api.hip solve_try_threads()         M + MR <= 640 and na <= 64 (and not wide_first)
-  solve_lds: use_lds 2 / 1 / 0      ba_api.hip solve_lds()                 150 KiB of LDS: tiled up to na = 165, packed at 180,
+  route = tiny / small_mid          ba_plan.hpp plan_solve                 no free landmark, na <= 16; kb_tiny also M + MR <= 640
+  block: kb_solve_try<256> / <512>  ba_plan.hpp plan_solve                 M + MR <= 640 and na <= 64 (and not wide_first)
+  use_lds 2 / 1 / 0, try_lds        ba_plan.hpp plan_solve                 150 KiB of LDS: tiled up to na = 165, packed at 180,
                                                                            in the global buffer (tiled, in place) from 195
   tile grid of the tiled layout     dense_lds.hip.h tl_tile_rows(na + 1)   na = 255: the rhs row is the last row of the grid
   rhs gather of the in-place layout ba_kernels.hip.h factor_stage_tiled    na > 512: more unknowns than kb_solve_try's threads
-  wide_trials()                     ba_api.hip wide_trials()               M >= 256 and F <= 32
-  wide_first()                      ba_api.hip wide_first()                wide_trials, M >= 600 and na >= 90
+  wide_trials                       ba_plan.hpp plan_solve                 M >= 256 and F <= 32
+  wide_first                        ba_plan.hpp plan_solve                 wide_trials, M >= 600 and na >= 90
 """
 import numpy as np
 import pytest
@@ -120,7 +121,7 @@ CASES = {
     "na90_prior": (lambda: window(6, 100, 9, True), route("multi", wt=1), 1e-7),
     "na90_M600_prior": (lambda: window(6, 200, 9, True), route("multi", wt=1, wf=1), 1e-7),
     "na90_M600": (lambda: window(7, 200, 9, False, fixed=1), route("multi", wt=1, wf=1), 1e-7),
-    # solve_lds: tiled in LDS up to 165 unknowns, packed triangle in LDS at 180, factored in place in the global buffer from 195;
+    # use_lds: tiled in LDS up to 165 unknowns, packed triangle in LDS at 180, factored in place in the global buffer from 195;
     # at na = 255 the rhs row is the last row of the tile grid
     "na165_prior": (lambda: window(11, 150, 2, True), route("multi", wt=1, wf=1), 1e-7),
     "na165": (lambda: window(12, 150, 2, False, fixed=1), route("multi", wt=1, wf=1), 1e-7),

@@ -249,7 +249,8 @@ class BaContext:
     ROUTES = {0: "none", 1: "tiny", 2: "chain", 3: "small_mid", 4: "multi"}
 
     def debug_last_route(self):
-        """The route the last solve() on this context took (xrhip_ba_debug_last_route): dict with route ("none", "tiny", "chain",
+        """The plan the last solve on this context was launched from (xrhip_ba_debug_last_route; solve(), and solve_begin() /
+        solve_linked() / solve_chained(), whose route is always "chain"): dict with route ("none", "tiny", "chain",
         "small_mid" = multi-launch with kb_small_mid, "multi"), use_lds (2 / 1 / 0, -1: not used), sred_tiled, block (kb_solve_try's
         workgroup size, 0: not launched), wide_trials, wide_first, na, F."""
         out = np.zeros(8, np.int32)
