@@ -150,6 +150,12 @@ void XRSLAMAmdSetInitialState(double t, const double q[4], const double p[3], co
                               const double bg[3], const double ba[3]);
 /* like XRSLAM_SENSOR_CAMERA but `gray_dev` is an 8-bit single-channel image already resident in HBM */
 void XRSLAMAmdPushImageDevice(const void *gray_dev, int stride, double timestamp);
+/* Colour frames.  XRSLAM_SENSOR_CAMERA accepts channel 3 (BGR) and 4 (BGRA, byte 3 ignored) like the reference's PushImage
+ * (cv::cvtColor); the frame is reduced to gray on the GPU as part of its upload, gray = (B*1868 + G*9617 + R*4899 + 8192) >> 14.
+ * This is the same for an interleaved 8-bit colour frame already resident in HBM (a decoder's or an ISP's output):
+ * channels 3 or 4 (1: same as XRSLAMAmdPushImageDevice), stride in bytes >= width * channels, any base alignment.  With device
+ * undistortion switched on the frame is reduced first and rectified second. */
+void XRSLAMAmdPushImageDeviceColor(const void *pixels_dev, int stride, int channels, double timestamp);
 /* What the reference's dataset readers ask the YamlConfig* for (xrslam-pc/player/src/IO/euroc_dataset_reader.cpp:4-7,16,62-66;
  * tum_dataset_reader.cpp:4-6,67-76): camera_time_offset(), camera_distortion_flag(), camera_distortion(),
  * camera_intrinsic(), camera_resolution().  The `config` out-parameter of XRSLAMCreate is an opaque handle here (the
@@ -239,6 +245,8 @@ void XRSLAMAmdInstanceGetResult(XRSLAMAmdInstance *inst, XRSLAMResultType result
 void XRSLAMAmdInstanceSetInitialState(XRSLAMAmdInstance *inst, double t, const double q[4], const double p[3],
                                       const double v[3], const double bg[3], const double ba[3]);
 void XRSLAMAmdInstancePushImageDevice(XRSLAMAmdInstance *inst, const void *gray_dev, int stride, double timestamp);
+void XRSLAMAmdInstancePushImageDeviceColor(XRSLAMAmdInstance *inst, const void *pixels_dev, int stride, int channels,
+                                           double timestamp);
 void XRSLAMAmdInstanceGetCameraConfig(XRSLAMAmdInstance *inst, XRSLAMAmdCameraConfig *out);
 int XRSLAMAmdInstanceDescribeConfig(XRSLAMAmdInstance *inst, char *buf, int cap);
 void XRSLAMAmdInstanceSetDeviceUndistort(XRSLAMAmdInstance *inst, const char *model);
@@ -276,6 +284,10 @@ void XRSLAMAmdGroupGetStats(XRSLAMAmdGroup *group, void *xrhip_group_stats_out, 
 int XRSLAMAmdInstanceReplay(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
                             const void *frames, size_t frame_bytes, int stride, int on_device, int *imu_cursor,
                             int *frame_cursor, int n_steps, double *poses_out8);
+/* The same loop over colour frames: channels 1, 3 (BGR) or 4 (BGRA); frame_bytes and stride describe the colour frames. */
+int XRSLAMAmdInstanceReplayColor(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
+                                 const void *frames, size_t frame_bytes, int stride, int channels, int on_device,
+                                 int *imu_cursor, int *frame_cursor, int n_steps, double *poses_out8);
 
 #ifdef __cplusplus
 }

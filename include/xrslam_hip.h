@@ -84,6 +84,16 @@ int xrhip_image_upload_device(xrhip_image *img, const void *gray_dev, int stride
  * and leaves the rectified frame where xrhip_image_preprocess reads it: one upload, no host pass over the pixels. */
 int xrhip_klt_set_undistort_map(xrhip_klt *ctx, const uint32_t *map2);
 int xrhip_image_upload_distorted(xrhip_image *img, const void *gray, int stride_bytes, int on_device);
+/* Colour frames (XRSLAMImage.channel 3 / 4; replaces: cv::cvtColor BGR2GRAY / BGRA2GRAY in XRSLAMManager::PushImage,
+ * xrslam-interface/src/XRSLAMManager.cpp:104-136).  `pixels` is interleaved 8-bit BGR (channels 3) or BGRA (channels 4, byte 3
+ * ignored) with any base alignment and any stride_bytes >= width * channels: a host pointer, or an HBM pointer when on_device.
+ * The frame is reduced to gray as part of its upload, gray = (B*1868 + G*9617 + R*4899 + 8192) >> 14, and lands where
+ * xrhip_image_preprocess reads it (for a member of a group: in the group's one upload launch, next to the members' gray frames).
+ * A host buffer may be reused on return; an HBM buffer must stay valid as for xrhip_image_upload_device.  channels 1 forwards to
+ * the gray functions.  _distorted: reduced to gray first, rectified second (needs xrhip_klt_set_undistort_map, else XRHIP_ESTATE).
+ * XRHIP_EINVAL for other channel counts, a null pointer, or stride_bytes < width * channels. */
+int xrhip_image_upload_color(xrhip_image *img, const void *pixels, int stride_bytes, int channels, int on_device);
+int xrhip_image_upload_color_distorted(xrhip_image *img, const void *pixels, int stride_bytes, int channels, int on_device);
 /* parity aid: the 8-bit frame xrhip_image_preprocess will read */
 int xrhip_debug_get_raw(xrhip_image *img, uint8_t *out);
 /* Development / parity aids of the pyramid build (xrhip_image_preprocess): on = 1 (default) builds the CLAHE plane, the three

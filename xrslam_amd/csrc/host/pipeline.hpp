@@ -44,7 +44,16 @@
 #include "two_view.hpp"
 #include "undistort_map.hpp"
 
+// The colour uploads are the one part of xrslam_hip.h these sources can do without: weak references, so that they also link and
+// load against a library behind that header which has the gray uploads only (the CPU reference build).  Pipeline::make_image
+// then reduces colour frames on the host; the product library always has them.
+extern "C" {
+int xrhip_image_upload_color(xrhip_image *img, const void *pixels, int stride_bytes, int channels, int on_device) __attribute__((weak));
+int xrhip_image_upload_color_distorted(xrhip_image *img, const void *pixels, int stride_bytes, int channels, int on_device) __attribute__((weak));
+}
+
 namespace xrh {
+inline bool have_color_upload() { return xrhip_image_upload_color != nullptr && xrhip_image_upload_color_distorted != nullptr; }
 
 struct HipError : std::runtime_error {
     explicit HipError(const std::string &m) : std::runtime_error(m) {}
@@ -289,16 +298,37 @@ struct Pipeline {
         xrhip_image_release(im);
         image_pool.push_back(im);
     }
-    std::shared_ptr<HipImage> make_image(const uint8_t *gray, int stride, double t, bool device_ptr) {
+    // channels 1: 8-bit gray; 3 / 4: interleaved BGR / BGRA, reduced to gray by the frame's upload (xrhip_image_upload_color) -- or
+    // here, where the library behind xrslam_hip.h has no colour upload (the CPU reference build: its host arithmetic is what the
+    // device's is compared against)
+    std::vector<uint8_t> gray_scratch;
+    std::shared_ptr<HipImage> make_image(const uint8_t *gray, int stride, double t, bool device_ptr, int channels = 1) {
+        if (channels != 1 && channels != 3 && channels != 4) throw std::runtime_error("Image channel is not supported!");
         auto img = std::make_shared<HipImage>();
         img->owner = this;
         img->h = acquire_image();
         img->t = t;
         img->w = (int)config.cam_resolution[0];
         img->hgt = (int)config.cam_resolution[1];
+        if (channels != 1 && !have_color_upload()) {   // cv::cvtColor BGR(A)2GRAY: (B*1868 + G*9617 + R*4899 + 8192) >> 14
+            const int cols = img->w, rows = img->hgt;
+            gray_scratch.resize((size_t)cols * rows);
+            for (int y = 0; y < rows; ++y)
+                for (int x = 0; x < cols; ++x) {
+                    const uint8_t *px = gray + (size_t)y * stride + (size_t)x * channels;
+                    gray_scratch[(size_t)y * cols + x] = (uint8_t)((px[0] * 1868 + px[1] * 9617 + px[2] * 4899 + 8192) >> 14);
+                }
+            gray = gray_scratch.data();
+            stride = cols;
+            channels = 1;
+        }
         // a member of an instance group starts its frame together with the other members (timing only: xrslam_hip.h, frame gate)
         if (group) xrhip_klt_frame_gate(klt);
-        if (undistort_on_device) hip_check(xrhip_image_upload_distorted(img->h, gray, stride, device_ptr ? 1 : 0), "xrhip_image_upload_distorted");
+        if (channels != 1) {
+            if (undistort_on_device)
+                hip_check(xrhip_image_upload_color_distorted(img->h, gray, stride, channels, device_ptr ? 1 : 0), "xrhip_image_upload_color_distorted");
+            else hip_check(xrhip_image_upload_color(img->h, gray, stride, channels, device_ptr ? 1 : 0), "xrhip_image_upload_color");
+        } else if (undistort_on_device) hip_check(xrhip_image_upload_distorted(img->h, gray, stride, device_ptr ? 1 : 0), "xrhip_image_upload_distorted");
         else if (device_ptr) hip_check(xrhip_image_upload_device(img->h, gray, stride), "xrhip_image_upload_device");
         else hip_check(xrhip_image_upload(img->h, gray, stride), "xrhip_image_upload");
         // FeatureTracker::work's first step (feature_tracker.cpp:39) depends on nothing but the frame: its launches are queued here,

@@ -23,7 +23,6 @@ struct Manager {
     std::shared_ptr<xrh::HipImage> cur_image;
     std::mutex input_mutex;
     std::string last_error;
-    std::vector<uint8_t> gray;
     int device = -1;   // HIP device the instance was created on (the current device is a per-thread setting)
     bool bound_by_replay = false;   // inside XRSLAMAmdInstanceReplay: the device is current for the whole loop
 };
@@ -93,24 +92,11 @@ void impl_push(Manager &m, XRSLAMSensorType type, void *data) {
         case XRSLAM_SENSOR_CAMERA: {
             auto *im = static_cast<XRSLAMImage *>(data);
             if (im->camera_id != 0) break;
-            const int cols = (int)m.config.cam_resolution[0], rows = (int)m.config.cam_resolution[1];
-            const uint8_t *src = im->data;
-            int stride = im->stride;
-            if (im->channel == 3 || im->channel == 4) {   // cv::cvtColor BGR(A)2GRAY: (B*1868 + G*9617 + R*4899 + 8192) >> 14
-                m.gray.resize((size_t)cols * rows);
-                for (int y = 0; y < rows; ++y)
-                    for (int x = 0; x < cols; ++x) {
-                        const uint8_t *px = im->data + (size_t)y * im->stride + (size_t)x * im->channel;
-                        m.gray[(size_t)y * cols + x] = (uint8_t)((px[0] * 1868 + px[1] * 9617 + px[2] * 4899 + 8192) >> 14);
-                    }
-                src = m.gray.data();
-                stride = cols;
-            } else if (im->channel != 1) {
-                throw std::runtime_error("Image channel is not supported!");
-            }
+            // channel 3 / 4 (BGR / BGRA): Pipeline::make_image hands the colour frame to the upload, which reduces it to gray
+            if (im->channel != 1 && im->channel != 3 && im->channel != 4) throw std::runtime_error("Image channel is not supported!");
             try {
                 std::lock_guard<std::mutex> lk(m.input_mutex);
-                m.cur_image = m.sys->P.make_image(src, stride, im->timeStamp, false);
+                m.cur_image = m.sys->P.make_image(im->data, im->stride, im->timeStamp, false, im->channel);
             } catch (...) {   // this frame did not arrive: XRSLAMRunOneFrame must not track the previous image a second time
                 std::lock_guard<std::mutex> lk(m.input_mutex);
                 m.cur_image.reset();
@@ -238,13 +224,14 @@ void impl_set_initial_state(Manager &m, double t, const double q[4], const doubl
     m.sys->init.states.push_back(s);
 }
 
-void impl_push_image_device(Manager &m, const void *gray_dev, int stride, double timestamp) {
+void impl_push_image_device(Manager &m, const void *gray_dev, int stride, double timestamp, int channels = 1) {
     if (!m.sys) return;
     bind_device(m);
     guarded(m, [&] {
         try {
             std::lock_guard<std::mutex> lk(m.input_mutex);
-            m.cur_image = m.sys->P.make_image(static_cast<const uint8_t *>(gray_dev), stride, timestamp, true);
+            if (channels != 1 && channels != 3 && channels != 4) throw std::runtime_error("Image channel is not supported!");
+            m.cur_image = m.sys->P.make_image(static_cast<const uint8_t *>(gray_dev), stride, timestamp, true, channels);
         } catch (...) {
             std::lock_guard<std::mutex> lk(m.input_mutex);
             m.cur_image.reset();
@@ -398,6 +385,9 @@ void XRSLAMAmdSetInitialState(double t, const double q[4], const double p[3], co
 void XRSLAMAmdPushImageDevice(const void *gray_dev, int stride, double timestamp) {
     impl_push_image_device(mgr(), gray_dev, stride, timestamp);
 }
+void XRSLAMAmdPushImageDeviceColor(const void *pixels_dev, int stride, int channels, double timestamp) {
+    impl_push_image_device(mgr(), pixels_dev, stride, timestamp, channels);
+}
 void XRSLAMAmdGetCameraConfig(XRSLAMAmdCameraConfig *out) { impl_get_camera_config(mgr(), out); }
 int XRSLAMAmdDescribeConfig(char *buf, int cap) { return impl_describe_config(mgr(), buf, cap); }
 void XRSLAMAmdSetDeviceUndistort(const char *model) { impl_set_device_undistort(mgr(), model); }
@@ -446,6 +436,10 @@ void XRSLAMAmdInstanceSetInitialState(XRSLAMAmdInstance *inst, double t, const d
 }
 void XRSLAMAmdInstancePushImageDevice(XRSLAMAmdInstance *inst, const void *gray_dev, int stride, double timestamp) {
     if (inst) impl_push_image_device(inst->m, gray_dev, stride, timestamp);
+}
+void XRSLAMAmdInstancePushImageDeviceColor(XRSLAMAmdInstance *inst, const void *pixels_dev, int stride, int channels,
+                                           double timestamp) {
+    if (inst) impl_push_image_device(inst->m, pixels_dev, stride, timestamp, channels);
 }
 void XRSLAMAmdInstanceGetCameraConfig(XRSLAMAmdInstance *inst, XRSLAMAmdCameraConfig *out) {
     if (inst) impl_get_camera_config(inst->m, out);
@@ -525,9 +519,9 @@ void XRSLAMAmdGroupGetStats(XRSLAMAmdGroup *grp, void *out, int reset) {
 // The player's loop (xrslam-pc/player/src/main.cpp:116-169) for n_steps camera frames of a pre-staged sequence, without a
 // host-language round trip per sensor sample: at equal timestamps gyroscope, then accelerometer, then camera
 // (IO/async_dataset_reader.cpp:41-48); RunOneFrame and the state / pose query after every image.
-int XRSLAMAmdInstanceReplay(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
-                            const void *frames, size_t frame_bytes, int stride, int on_device, int *imu_cursor,
-                            int *frame_cursor, int n_steps, double *poses_out8) {
+int XRSLAMAmdInstanceReplayColor(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
+                                 const void *frames, size_t frame_bytes, int stride, int channels, int on_device,
+                                 int *imu_cursor, int *frame_cursor, int n_steps, double *poses_out8) {
     if (!inst || !imu7 || !cam_t || !frames || !imu_cursor || !frame_cursor) return -1;
     Manager &m = inst->m;
     int n_poses = 0;
@@ -555,14 +549,14 @@ int XRSLAMAmdInstanceReplay(XRSLAMAmdInstance *inst, const double *imu7, int n_i
         *imu_cursor = k;
         const unsigned char *img = static_cast<const unsigned char *>(frames) + (size_t)fk * frame_bytes;
         if (on_device) {
-            impl_push_image_device(m, img, stride, t);
+            impl_push_image_device(m, img, stride, t, channels);
         } else {
             XRSLAMImage im;
             im.data = const_cast<unsigned char *>(img);
             im.timeStamp = t;
             im.stride = stride;
             im.camera_id = 0;
-            im.channel = 1;
+            im.channel = channels;
             im.ext = nullptr;
             impl_push(m, XRSLAM_SENSOR_CAMERA, &im);
         }
@@ -580,6 +574,13 @@ int XRSLAMAmdInstanceReplay(XRSLAMAmdInstance *inst, const double *imu7, int n_i
         *frame_cursor = fk + 1;
     }
     return n_poses;
+}
+
+int XRSLAMAmdInstanceReplay(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
+                            const void *frames, size_t frame_bytes, int stride, int on_device, int *imu_cursor,
+                            int *frame_cursor, int n_steps, double *poses_out8) {
+    return XRSLAMAmdInstanceReplayColor(inst, imu7, n_imu, cam_t, n_frames, frames, frame_bytes, stride, 1, on_device, imu_cursor,
+                                        frame_cursor, n_steps, poses_out8);
 }
 
 }   // extern "C"

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstring>
 #include <optional>
+#include <string>
 #if defined(__x86_64__)
 #include <immintrin.h>
 #endif
@@ -80,6 +81,7 @@ struct xrhip_klt {
     // 752x480 frame against ~25 for the memcpy, measured as the difference to device-resident input, round 3.)
     static constexpr int UP_SLOTS = 3;
     uint8_t *up_buf[UP_SLOTS] = {nullptr, nullptr, nullptr};
+    size_t up_cap = 0;   // bytes per slot
     hipEvent_t up_done[UP_SLOTS] = {nullptr, nullptr, nullptr};
     bool up_busy[UP_SLOTS] = {false, false, false};
     int up_next = 0;
@@ -488,8 +490,9 @@ int xrhip_klt_create(int width, int height, int max_points, xrhip_klt **out) {
     XR_HIP(hipMalloc(&c->d_counters, sizeof(LkCounters)));
     XR_HIP(hipMemset(c->d_counters, 0, sizeof(LkCounters)));
     XR_HIP(hipHostMalloc(&c->h_counters, sizeof(LkCounters), hipHostMallocDefault));
+    c->up_cap = (size_t)width * height;
     for (int i = 0; i < xrhip_klt::UP_SLOTS; ++i) {
-        XR_HIP(hipHostMalloc(&c->up_buf[i], (size_t)width * height, hipHostMallocDefault));
+        XR_HIP(hipHostMalloc(&c->up_buf[i], (size_t)width * height, hipHostMallocDefault));   // (grows with the first colour frame)
         XR_HIP(hipEventCreateWithFlags(&c->up_done[i], hipEventDisableTiming));
     }
     rc = ensure_points(c, std::max(256, max_points * 2));
@@ -616,8 +619,39 @@ static void copy_to_pinned(uint8_t *dst, const uint8_t *src, size_t n) {
     std::memcpy(dst, src, n);
 }
 
-// Copies a host frame into the next pinned slot and queues its DMA into `dst` (w*h, dense); the caller's buffer is free on return.
-static int stage_host_frame(xrhip_klt *c, const uint8_t *gray, int stride, uint8_t *dst) {
+// The pinned slots hold a gray frame until the first colour frame arrives: a gray-only caller never pays for the colour size.
+static int ensure_slot_bytes(xrhip_klt *c, size_t bytes) {
+    if (bytes <= c->up_cap) return XRHIP_OK;
+    // nothing may still be reading the slots that are about to go
+    if (c->group) {
+        int rc = flush_upload(c);
+        if (rc) return rc;
+        rc = group_drain(c->group, GQ_KLT, c);
+        if (rc) return rc;
+        c->uploads_unsynced = 0;
+    } else {
+        XR_HIP(hipStreamSynchronize(c->stream));
+    }
+    for (int i = 0; i < xrhip_klt::UP_SLOTS; ++i) {
+        hipHostFree(c->up_buf[i]);
+        c->up_buf[i] = nullptr;
+        c->up_busy[i] = false;
+    }
+    c->up_cap = 0;
+    for (int i = 0; i < xrhip_klt::UP_SLOTS; ++i) XR_HIP(hipHostMalloc(&c->up_buf[i], bytes, hipHostMallocDefault));
+    c->up_cap = bytes;
+    return XRHIP_OK;
+}
+
+// Copies a host frame into the next pinned slot and queues its transfer into `dst` (w*h, dense); the caller's buffer is free on return.
+// bpp 1: a gray frame, DMA (or the group's upload launch).  bpp 3 / 4: a BGR / BGRA frame, reduced to gray by k_upload, which reads
+// the mapped slot -- the plane in HBM is written once and the colour bytes cross the host link once.
+static int stage_host_frame(xrhip_klt *c, const uint8_t *pixels, int stride, uint8_t *dst, int bpp = 1) {
+    const size_t row = (size_t)c->w * bpp;
+    if (bpp != 1) {
+        const int rc = ensure_slot_bytes(c, row * c->h);
+        if (rc) return rc;
+    }
     const int slot = c->up_next;
     c->up_next = (slot + 1) % xrhip_klt::UP_SLOTS;
     if (c->group) {
@@ -631,26 +665,34 @@ static int stage_host_frame(xrhip_klt *c, const uint8_t *gray, int stride, uint8
         int rc = group_wait_launched(&c->rq_upload);   // (its argument block is about to be rewritten)
         if (rc) return rc;
         uint8_t *buf = c->up_buf[slot];
-        if (stride == c->w) copy_to_pinned(buf, gray, (size_t)c->w * c->h);
+        if ((size_t)stride == row) copy_to_pinned(buf, pixels, row * c->h);
         else
-            for (int y = 0; y < c->h; ++y) std::memcpy(buf + (size_t)y * c->w, gray + (size_t)y * stride, (size_t)c->w);
+            for (int y = 0; y < c->h; ++y) std::memcpy(buf + (size_t)y * row, pixels + (size_t)y * stride, row);
         uint8_t *dbuf = nullptr;
         XR_HIP(hipHostGetDevicePointer((void **)&dbuf, buf, 0));
         rc = flush_upload(c);   // (an earlier frame nobody preprocessed)
         if (rc) return rc;
-        c->a_upload = UploadArgs{dbuf, c->w, dst, c->w, c->h};
+        c->a_upload = UploadArgs{dbuf, (int)row, dst, c->w, c->h, bpp};
         c->uploads_unsynced++;
         c->upload_pending = true;   // submitted with the frame's preprocessing (xrhip_image_preprocess), or by whoever reads the plane first
         return XRHIP_OK;
     }
     if (c->up_busy[slot]) XR_HIP(hipEventSynchronize(c->up_done[slot]));   // three uploads ago: long done unless nothing consumed them
     uint8_t *buf = c->up_buf[slot];
-    if (stride == c->w) {
-        copy_to_pinned(buf, gray, (size_t)c->w * c->h);
+    if ((size_t)stride == row) {
+        copy_to_pinned(buf, pixels, row * c->h);
     } else {
-        for (int y = 0; y < c->h; ++y) std::memcpy(buf + (size_t)y * c->w, gray + (size_t)y * stride, (size_t)c->w);
+        for (int y = 0; y < c->h; ++y) std::memcpy(buf + (size_t)y * row, pixels + (size_t)y * stride, row);
     }
-    XR_HIP(hipMemcpyAsync(dst, buf, (size_t)c->w * c->h, hipMemcpyHostToDevice, c->stream));
+    if (bpp == 1) {
+        XR_HIP(hipMemcpyAsync(dst, buf, (size_t)c->w * c->h, hipMemcpyHostToDevice, c->stream));
+    } else {
+        uint8_t *dbuf = nullptr;
+        XR_HIP(hipHostGetDevicePointer((void **)&dbuf, buf, 0));
+        c->a_upload = UploadArgs{dbuf, (int)row, dst, c->w, c->h, bpp};
+        const int rc = klt_issue(c, c->rq_upload, GK_UPLOAD, &c->a_upload, launch_upload_batch);
+        if (rc) return rc;
+    }
     XR_HIP(hipEventRecord(c->up_done[slot], c->stream));
     c->up_busy[slot] = true;
     return XRHIP_OK;
@@ -769,6 +811,55 @@ int xrhip_image_upload_device(xrhip_image *im, const void *gray_dev, int stride)
     im->want_detect = false;
     im->detect_seq = 0;
     return XRHIP_OK;
+}
+
+// A BGR / BGRA frame into `dst` as gray: from a host buffer through the pinned slots, or from HBM where it lies
+static int upload_color_into(xrhip_klt *c, const void *pixels, int stride, int channels, int on_device, uint8_t *dst) {
+    if (!on_device) return stage_host_frame(c, static_cast<const uint8_t *>(pixels), stride, dst, channels);
+    if (c->group) {
+        int rc = group_wait_launched(&c->rq_upload);
+        if (rc) return rc;
+        rc = flush_upload(c);
+        if (rc) return rc;
+    }
+    c->a_upload = UploadArgs{static_cast<const uint8_t *>(pixels), stride, dst, c->w, c->h, channels};
+    if (c->group) {
+        c->upload_pending = true;   // with the frame's preprocessing, like xrhip_image_upload_device
+        return XRHIP_OK;
+    }
+    return klt_issue(c, c->rq_upload, GK_UPLOAD, &c->a_upload, launch_upload_batch);
+}
+static int check_color_args(const char *who, const xrhip_image *im, const void *pixels, int stride, int channels) {
+    if (!im || !pixels) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": null argument").c_str());
+    if (channels != 3 && channels != 4) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": channels must be 1, 3 (BGR) or 4 (BGRA)").c_str());
+    if ((long long)stride < (long long)im->ctx->w * channels) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": stride_bytes < width * channels").c_str());
+    return XRHIP_OK;
+}
+
+int xrhip_image_upload_color(xrhip_image *im, const void *pixels, int stride, int channels, int on_device) {
+    if (channels == 1 && im && pixels)
+        return on_device ? xrhip_image_upload_device(im, pixels, stride) : xrhip_image_upload(im, static_cast<const uint8_t *>(pixels), stride);
+    int rc = check_color_args("xrhip_image_upload_color", im, pixels, stride, channels);
+    if (rc) return rc;
+    rc = upload_color_into(im->ctx, pixels, stride, channels, on_device, im->raw);
+    if (rc) return rc;
+    im->have_raw = true;
+    im->have_pyramid = false;
+    im->want_detect = false;
+    im->detect_seq = 0;
+    return XRHIP_OK;
+}
+
+int xrhip_image_upload_color_distorted(xrhip_image *im, const void *pixels, int stride, int channels, int on_device) {
+    if (channels == 1 && im && pixels) return xrhip_image_upload_distorted(im, pixels, stride, on_device);
+    int rc = check_color_args("xrhip_image_upload_color_distorted", im, pixels, stride, channels);
+    if (rc) return rc;
+    xrhip_klt *c = im->ctx;
+    if (!c->have_undist) return xr_fail(XRHIP_ESTATE, "xrhip_image_upload_color_distorted: no undistortion map (xrhip_klt_set_undistort_map)");
+    // gray first, rectified second: the reduced frame takes the place of the frame a gray camera would have recorded
+    rc = upload_color_into(c, pixels, stride, channels, on_device, c->undist_src);
+    if (rc) return rc;
+    return xrhip_image_upload_distorted(im, c->undist_src, c->w, 1);
 }
 
 int xrhip_image_preprocess(xrhip_image *im, double clip_limit, int tiles_x, int tiles_y) {

@@ -1422,10 +1422,65 @@ struct UploadArgs {
     int sstride;
     uint8_t *dst;   // dense w x h
     int w, h;
+    int bpp;        // bytes per source pixel: 0 / 1 gray (a copy), 3 BGR, 4 BGRA (reduced to gray on the way)
 };
+// cv::cvtColor BGR(A)2GRAY in its 14-bit fixed point (the host pipeline's and the player's arithmetic); at most 255
+__device__ __forceinline__ uint32_t bgr_to_gray(uint32_t b, uint32_t g, uint32_t r) {
+    return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14;
+}
+// A colour frame (any base alignment, any stride >= w * BPP) reduced into the dense gray plane.  A lane owns four consecutive pixels of
+// the plane = one dword store.  Where the four lie in one row it fetches the aligned dwords that cover their 12 / 16 source bytes --
+// neighbouring lanes read neighbouring dwords, and every fetched dword holds at least one byte of the frame, so nothing outside the
+// pages of the frame is touched -- and shifts them into place; four pixels that straddle a row end (w % 4 != 0) and the plane's last
+// w * h % 4 pixels go byte by byte.
+template <int BPP> __device__ __forceinline__ void d_upload_color(const UploadArgs &a) {
+    const uint32_t w = (uint32_t)a.w, total = w * (uint32_t)a.h;
+    const uint32_t n4 = (total + 3u) >> 2;
+    constexpr int ND = BPP;   // dwords of four pixels
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n4; i += gridDim.x * 256u) {
+        const uint32_t p0 = i << 2;
+        const uint32_t y = p0 / w, x = p0 - y * w;
+        if (x + 4u <= w) {   // (p0 + 4 <= total follows)
+            const uintptr_t ad = reinterpret_cast<uintptr_t>(a.src + (size_t)y * (size_t)a.sstride + (size_t)x * BPP);
+            const uint32_t *q = reinterpret_cast<const uint32_t *>(ad & ~(uintptr_t)3);
+            const uint32_t sh = (uint32_t)(ad & 3) * 8u;
+            uint32_t d[ND + 1];
+#pragma unroll
+            for (int k = 0; k < ND; ++k) d[k] = q[k];
+            d[ND] = 0;
+            if (sh) {
+                d[ND] = q[ND];
+#pragma unroll
+                for (int k = 0; k < ND; ++k) d[k] = (d[k] >> sh) | (d[k + 1] << (32u - sh));
+            }
+            uint32_t g0, g1, g2, g3;
+            if (BPP == 4) {
+                g0 = bgr_to_gray(d[0] & 255u, (d[0] >> 8) & 255u, (d[0] >> 16) & 255u);
+                g1 = bgr_to_gray(d[1] & 255u, (d[1] >> 8) & 255u, (d[1] >> 16) & 255u);
+                g2 = bgr_to_gray(d[2] & 255u, (d[2] >> 8) & 255u, (d[2] >> 16) & 255u);
+                g3 = bgr_to_gray(d[ND - 1] & 255u, (d[ND - 1] >> 8) & 255u, (d[ND - 1] >> 16) & 255u);
+            } else {
+                g0 = bgr_to_gray(d[0] & 255u, (d[0] >> 8) & 255u, (d[0] >> 16) & 255u);
+                g1 = bgr_to_gray(d[0] >> 24, d[1] & 255u, (d[1] >> 8) & 255u);
+                g2 = bgr_to_gray((d[1] >> 16) & 255u, d[1] >> 24, d[2] & 255u);
+                g3 = bgr_to_gray((d[2] >> 8) & 255u, (d[2] >> 16) & 255u, d[2] >> 24);
+            }
+            reinterpret_cast<uint32_t *>(a.dst)[i] = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
+        } else {
+            const uint32_t pe = p0 + 4u < total ? p0 + 4u : total;
+            for (uint32_t p = p0; p < pe; ++p) {
+                const uint32_t py = p / w, px = p - py * w;
+                const uint8_t *s = a.src + (size_t)py * (size_t)a.sstride + (size_t)px * BPP;
+                a.dst[p] = (uint8_t)bgr_to_gray(s[0], s[1], s[2]);
+            }
+        }
+    }
+}
 __global__ __launch_bounds__(256) void k_upload(Batch<UploadArgs> b) {
     const UploadArgs &a = b.e[blockIdx.z];
     if (!a.src) return;
+    if (a.bpp == 3) return d_upload_color<3>(a);
+    if (a.bpp == 4) return d_upload_color<4>(a);
     const size_t total = (size_t)a.w * a.h;
     if (a.sstride == a.w && (total & 15) == 0 && ((reinterpret_cast<uintptr_t>(a.src) | reinterpret_cast<uintptr_t>(a.dst)) & 15) == 0) {
         const uint4 *s4 = reinterpret_cast<const uint4 *>(a.src);

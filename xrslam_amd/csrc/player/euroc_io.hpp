@@ -166,14 +166,16 @@ inline std::vector<Event> merge_events(const std::vector<CameraRow> &cam, const 
 // ------------------------------------------------------------------------------------------------ PNG
 struct GrayImage {
     int w = 0, h = 0;
-    std::vector<uint8_t> px;   // row-major, stride w
+    int channels = 1;          // 1 gray; 3 / 4: interleaved BGR / BGRA (decode_png with keep_color)
+    std::vector<uint8_t> px;   // row-major, stride w * channels
 };
 
 inline uint32_t be32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 
 // 8-bit, non-interlaced, colour types 0 (grey), 2 (RGB), 4 (grey+alpha), 6 (RGBA).  Colour is reduced with the
-// integer weights of cv::cvtColor(BGR2GRAY): (R*4899 + G*9617 + B*1868 + 8192) >> 14.
-inline GrayImage decode_png(const std::vector<uint8_t> &file) {
+// integer weights of cv::cvtColor(BGR2GRAY): (R*4899 + G*9617 + B*1868 + 8192) >> 14 -- or, with keep_color, handed out as
+// the BGR / BGRA pixels cv::imread(IMREAD_UNCHANGED) would give, for a caller that pushes them with channel 3 / 4.
+inline GrayImage decode_png(const std::vector<uint8_t> &file, bool keep_color = false) {
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
     if (file.size() < 8 || std::memcmp(file.data(), sig, 8) != 0) throw std::runtime_error("png: bad signature");
     size_t pos = 8;
@@ -220,7 +222,9 @@ inline GrayImage decode_png(const std::vector<uint8_t> &file) {
     GrayImage img;
     img.w = w;
     img.h = h;
-    img.px.resize((size_t)w * h);
+    const bool color = keep_color && ch >= 3;
+    if (color) img.channels = ch;
+    img.px.resize((size_t)w * h * img.channels);
     for (int y = 0; y < h; ++y) {
         const uint8_t *line = &raw[(stride + 1) * (size_t)y];
         const int filter = line[0];
@@ -238,10 +242,16 @@ inline GrayImage decode_png(const std::vector<uint8_t> &file) {
             }
             cur[i] = (uint8_t)(line[1 + i] + pred);
         }
-        uint8_t *dst = &img.px[(size_t)y * w];
+        uint8_t *dst = &img.px[(size_t)y * w * img.channels];
         for (int x = 0; x < w; ++x) {
             const uint8_t *px = &cur[(size_t)x * bpp];
-            if (ch <= 2) dst[x] = px[0];
+            if (color) {   // RGB(A) in the file, BGR(A) in memory
+                uint8_t *d = dst + (size_t)x * ch;
+                d[0] = px[2 * bps];
+                d[1] = px[bps];
+                d[2] = px[0];
+                if (ch == 4) d[3] = px[3 * bps];
+            } else if (ch <= 2) dst[x] = px[0];
             else dst[x] = (uint8_t)((px[0] * 4899 + px[bps] * 9617 + px[2 * bps] * 1868 + 8192) >> 14);
         }
         prev.swap(cur);

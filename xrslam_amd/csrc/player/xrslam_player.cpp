@@ -7,7 +7,9 @@
 //
 //   xrslam-player --slam configs/euroc_slam.yaml --device configs/euroc_sensor.yaml --euroc <dir>/mav0
 //                 [--out traj.tum] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined]
+//                 [--push-color]
 //
+// (--push-color: a colour PNG is pushed as BGR / BGRA with channel 3 / 4 and reduced to gray by the library instead of by the reader.)
 // (--pipelined: XRSLAMAmdSetThreading(1), the reference's XRSLAM_ENABLE_THREADING build with deterministic hand-offs.)
 // The reference player's own command line (main.cpp:57-79) is accepted as well, so its invocations carry over:
 //
@@ -49,7 +51,7 @@ static const TruthRow *nearest_truth(const std::vector<TruthRow> &gt, double t, 
 
 int main(int argc, char **argv) {
     std::map<std::string, std::string> opt;
-    bool undistort = true, host_undistort = false, pipelined = false;
+    bool undistort = true, host_undistort = false, pipelined = false, push_color = false;
     // the reference's option names (main.cpp:57-71) map onto ours
     const std::map<std::string, std::string> alias = {{"-sc", "slam"}, {"--slamconfig", "slam"}, {"-dc", "device"},
                                                       {"--deviceconfig", "device"}, {"-lc", "license"}, {"--license", "license"},
@@ -59,6 +61,7 @@ int main(int argc, char **argv) {
         if (a == "--no-undistort") undistort = false;
         else if (a == "--host-undistort") host_undistort = true;   // the reference's arrangement: the reader rectifies on the host
         else if (a == "--pipelined") pipelined = true;
+        else if (a == "--push-color") push_color = true;   // colour PNGs are pushed as BGR / BGRA (channel 3 / 4): the library reduces them
         else if (a == "-p" || a == "--play") continue;
         else if (alias.count(a) && i + 1 < argc) opt[alias.at(a)] = argv[++i];
         else if (a.rfind("--", 0) == 0 && i + 1 < argc) opt[a.substr(2)] = argv[++i];
@@ -80,7 +83,7 @@ int main(int argc, char **argv) {
     }
     if (!opt.count("slam") || !opt.count("device") || !opt.count("euroc")) {
         std::fprintf(stderr, "usage: xrslam-player --slam cfg.yaml --device sensor.yaml --euroc <dir>/mav0 [--out traj.tum] "
-                             "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined]\n"
+                             "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color]\n"
                              "   or: xrslam-player -sc cfg.yaml -dc sensor.yaml [--tum traj.tum] [--csv traj.csv] [-p] "
                              "euroc://<dir>/mav0 | tum://<dir>/mav0\n");
         return 2;
@@ -156,7 +159,7 @@ int main(int argc, char **argv) {
             const auto io0 = std::chrono::steady_clock::now();
             GrayImage img;
             try {
-                img = decode_png(read_file(root + "/cam0/data/" + cam[ev.index].filename));
+                img = decode_png(read_file(root + "/cam0/data/" + cam[ev.index].filename), push_color);
             } catch (const std::exception &e) {
                 std::fprintf(stderr, "%s: %s\n", cam[ev.index].filename.c_str(), e.what());
                 break;
@@ -168,8 +171,18 @@ int main(int argc, char **argv) {
                              img.h, (int)cfg.cam_resolution[0], (int)cfg.cam_resolution[1]);
                 break;
             }
+            const bool rectify_here = undistort && cfg.cam_distortion_flag && !device_undistort;
+            if (img.channels != 1 && rectify_here) {   // the host remap takes gray: reduced first, rectified second, as in the library
+                std::vector<uint8_t> g((size_t)img.w * img.h);
+                for (size_t i = 0; i < g.size(); ++i) {
+                    const uint8_t *c = &img.px[i * img.channels];
+                    g[i] = (uint8_t)((c[0] * 1868 + c[1] * 9617 + c[2] * 4899 + 8192) >> 14);
+                }
+                img.px.swap(g);
+                img.channels = 1;
+            }
             const uint8_t *pixels = img.px.data();
-            if (undistort && cfg.cam_distortion_flag && !device_undistort) {
+            if (rectify_here) {
                 if (!und) {
                     if (model == "cv_undistort") und.reset(new Undistorter(img.w, img.h, K4, cfg.cam_distortion));
                     else und.reset(new Undistorter(img.w, img.h, K4, std::vector<double>(cfg.cam_distortion, cfg.cam_distortion + 4), model));
@@ -184,8 +197,8 @@ int main(int argc, char **argv) {
             xi.camera_id = 0;
             xi.timeStamp = ev.t;
             xi.data = const_cast<uint8_t *>(pixels);
-            xi.channel = 1;
-            xi.stride = img.w;
+            xi.channel = img.channels;
+            xi.stride = img.w * img.channels;
             XRSLAMPushSensorData(XRSLAM_SENSOR_CAMERA, &xi);
             if (has_gyro && has_acc) {
                 XRSLAMRunOneFrame();

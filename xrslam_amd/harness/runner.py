@@ -69,6 +69,9 @@ def load(lib_path):
     lib.XRSLAMAmdSetInitialState.restype = None
     lib.XRSLAMAmdPushImageDevice.argtypes = [C.c_void_p, C.c_int, C.c_double]
     lib.XRSLAMAmdPushImageDevice.restype = None
+    if hasattr(lib, "XRSLAMAmdPushImageDeviceColor"):
+        lib.XRSLAMAmdPushImageDeviceColor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double]
+        lib.XRSLAMAmdPushImageDeviceColor.restype = None
     lib.XRSLAMAmdGetTimes.argtypes = [C.POINTER(XRSLAMAmdTimes)]
     lib.XRSLAMAmdGetTimes.restype = None
     lib.XRSLAMAmdLastError.restype = C.c_char_p
@@ -104,6 +107,12 @@ def load(lib_path):
         lib.XRSLAMAmdInstanceReplay.argtypes = [H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p]
         lib.XRSLAMAmdInstanceReplay.restype = C.c_int
+        if hasattr(lib, "XRSLAMAmdInstanceReplayColor"):
+            lib.XRSLAMAmdInstancePushImageDeviceColor.argtypes = [H, C.c_void_p, C.c_int, C.c_int, C.c_double]
+            lib.XRSLAMAmdInstancePushImageDeviceColor.restype = None
+            lib.XRSLAMAmdInstanceReplayColor.argtypes = [H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int,
+                                                         C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p]
+            lib.XRSLAMAmdInstanceReplayColor.restype = C.c_int
     if hasattr(lib, "XRSLAMAmdGroupCreate"):
         lib.XRSLAMAmdGroupCreate.argtypes = [C.POINTER(C.c_void_p)]
         lib.XRSLAMAmdGroupDestroy.argtypes = [C.c_void_p]
@@ -162,17 +171,21 @@ class _Api:
                  "set_device_undistort": ("XRSLAMAmdSetDeviceUndistort", "XRSLAMAmdInstanceSetDeviceUndistort"),
                  "set_threading": ("XRSLAMAmdSetThreading", "XRSLAMAmdInstanceSetThreading"),
                  "sync": ("XRSLAMAmdFlush", "XRSLAMAmdInstanceFlush")}
+        if hasattr(lib, "XRSLAMAmdPushImageDeviceColor"):
+            names["push_image_device_color"] = ("XRSLAMAmdPushImageDeviceColor", "XRSLAMAmdInstancePushImageDeviceColor")
         for attr, (glob, inst) in names.items():
             setattr(self, attr, getattr(lib, glob) if handle is None else functools.partial(getattr(lib, inst), handle))
 
 
 class Session:
     """One XRSLAM instance: the process singleton behind the reference's six symbols (XRSLAMManager.cpp:6-9), or --
-    instance=True -- an XRSLAMAmdInstance of its own, so that several sessions can live in one process."""
+    instance=True -- an XRSLAMAmdInstance of its own, so that several sessions can live in one process.
+    channels 3 / 4: seq["frames"] (or device_frames) hold interleaved BGR / BGRA frames, [n][h][w][channels]."""
 
     def __init__(self, lib_path, seq, slam_yaml=SLAM_YAML, sensor_yaml=SENSOR_YAML, device_frames=None,
-                 init_frames=60, instance=False, device_undistort=None, threading=0, group=None):
+                 init_frames=60, instance=False, device_undistort=None, threading=0, group=None, channels=1):
         self.lib = load(lib_path)
+        self.channels = int(channels)
         self.seq = seq
         cfg = C.c_void_p()
         if instance:
@@ -237,10 +250,13 @@ class Session:
         self._push_imu_until(t)
         if self.device_frames is not None:
             base, fbytes, stride = self.device_frames
-            self.api.push_image_device(C.c_void_p(base + self.frame_k * fbytes), stride, t)
+            if self.channels == 1:
+                self.api.push_image_device(C.c_void_p(base + self.frame_k * fbytes), stride, t)
+            else:
+                self.api.push_image_device_color(C.c_void_p(base + self.frame_k * fbytes), stride, self.channels, t)
         else:
             fr = self.seq["frames"][self.frame_k]
-            img = XRSLAMImage(fr.ctypes.data, t, fr.strides[0], 0, 1, None)
+            img = XRSLAMImage(fr.ctypes.data, t, fr.strides[0], 0, self.channels, None)
             self.api.push(XRSLAM_SENSOR_CAMERA, C.byref(img))
         self.api.run()
         state = C.c_int(-1)
@@ -268,8 +284,13 @@ class Session:
             ptr, on_dev = C.c_void_p(base), 1
         else:
             ptr, fbytes, stride, on_dev = C.c_void_p(frames.ctypes.data), frames.strides[0], frames.strides[1], 0
-        k = self.lib.XRSLAMAmdInstanceReplay(self._handle, imu.ctypes.data, len(imu), cam_t.ctypes.data, len(cam_t), ptr, fbytes,
-                                             stride, on_dev, C.byref(ic), C.byref(fc), int(n), out.ctypes.data)
+        if self.channels == 1:
+            k = self.lib.XRSLAMAmdInstanceReplay(self._handle, imu.ctypes.data, len(imu), cam_t.ctypes.data, len(cam_t), ptr, fbytes,
+                                                 stride, on_dev, C.byref(ic), C.byref(fc), int(n), out.ctypes.data)
+        else:
+            k = self.lib.XRSLAMAmdInstanceReplayColor(self._handle, imu.ctypes.data, len(imu), cam_t.ctypes.data, len(cam_t), ptr,
+                                                      fbytes, stride, self.channels, on_dev, C.byref(ic), C.byref(fc), int(n),
+                                                      out.ctypes.data)
         if k < 0:
             raise RuntimeError("XRSLAMAmdInstanceReplay: bad arguments")
         self.imu_k, self.frame_k = ic.value, fc.value

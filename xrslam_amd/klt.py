@@ -44,6 +44,8 @@ def _bind():
     L.xrhip_klt_synchronize.argtypes = [vp]
     L.xrhip_klt_set_undistort_map.argtypes = [vp, vp]
     L.xrhip_image_upload_distorted.argtypes = [vp, vp, C.c_int, C.c_int]
+    L.xrhip_image_upload_color.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
+    L.xrhip_image_upload_color_distorted.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.xrhip_debug_get_raw.argtypes = [vp, vp]
     L.xrhip_debug_set_fused_pyramid.argtypes = [vp, C.c_int]
     L.xrhip_debug_get_level_padded.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -154,6 +156,24 @@ class HipImage:
 
     def upload_distorted_device(self, dev_ptr, stride):
         check(L().xrhip_image_upload_distorted(self._h, C.c_void_p(dev_ptr), int(stride), 1))
+
+    def _color_args(self, pixels, on_device, stride, channels):
+        if on_device:   # pixels: a device pointer (int) to interleaved BGR / BGRA rows
+            return C.c_void_p(int(pixels)), int(stride), int(channels)
+        assert pixels.dtype == np.uint8 and pixels.ndim == 3 and pixels.shape[:2] == (self.ctx.h, self.ctx.w), pixels.shape
+        assert pixels.strides[2] == 1 and pixels.strides[1] == pixels.shape[2], pixels.strides   # rows may be padded, pixels not
+        return _p(pixels), pixels.strides[0], pixels.shape[2]
+
+    def upload_color(self, pixels, on_device=False, stride=None, channels=None):
+        """An interleaved BGR / BGRA frame, reduced to gray on its way in: a uint8 array [h][w][3 or 4] (rows may be strided),
+        or -- on_device -- a device pointer with its row stride in bytes and its channel count."""
+        ptr, stride, channels = self._color_args(pixels, on_device, stride, channels)
+        check(L().xrhip_image_upload_color(self._h, ptr, stride, channels, 1 if on_device else 0))
+
+    def upload_color_distorted(self, pixels, on_device=False, stride=None, channels=None):
+        """upload_color for a frame as the camera recorded it: reduced to gray, then rectified (KltContext.set_undistort_map)."""
+        ptr, stride, channels = self._color_args(pixels, on_device, stride, channels)
+        check(L().xrhip_image_upload_color_distorted(self._h, ptr, stride, channels, 1 if on_device else 0))
 
     def raw(self):
         """The 8-bit frame preprocess() will read (parity aid)."""
