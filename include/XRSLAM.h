@@ -227,6 +227,45 @@ const char *XRSLAMAmdLastError(void);
 void XRSLAMAmdSetThreading(int mode);
 void XRSLAMAmdFlush(void);
 
+/* ---- tracking view (additive) ----
+ * XRSLAM_RESULT_FEATURES fills XRSLAMFeatures::pos with the pixel positions of the key points of the newest tracked frame that have a
+ * track, in key-point order: the set the reference's feature_tracker_painter paints (core/feature_tracker.cpp:137-149).
+ * XRSLAMAmdGetFeatures is its C-callable form with everything the tracker knows about the frame: ALL key points of the newest tracked
+ * frame in key-point order (those just detected have track_id -1, age 0), `age` = the track's key-point count in the tracking map (what
+ * Frame::track_keypoints sorts by), and -- with XRSLAMAmdSetFeatureHistory(frames), 0 (default) .. 8 = XRSLAM_AMD_VIEW_MAX_TRAIL -- `trail`:
+ * the positions of the same track in the previous frames of the tracking map, newest first, up to the first frame without it.  Writes at
+ * most `cap` entries (out may be NULL) and *timestamp (may be NULL); returns the count needed, 0 before the first tracked frame.  The
+ * history setting takes effect with the next tracked frame. */
+#define XRSLAM_AMD_VIEW_MAX_TRAIL 8
+typedef struct XRSLAMAmdFeature {
+    double x, y;
+    long long track_id;
+    int age;
+    int n_trail;
+    double trail[XRSLAM_AMD_VIEW_MAX_TRAIL][2];
+} XRSLAMAmdFeature;
+int XRSLAMAmdGetFeatures(XRSLAMAmdFeature *out, int cap, double *timestamp);
+void XRSLAMAmdSetFeatureHistory(int frames);
+/* The tracker's view of its newest frame, drawn on the GPU (xrslam_hip.h: xrhip_image_render_view) into interleaved 8-bit BGR
+ * (channels 3) or BGRA (channels 4) rows of `stride` bytes: a host buffer, or one in HBM when on_device (complete after the next call that
+ * waits for the instance, e.g. XRSLAMAmdGetKltStats; at once for a member of a group).
+ *   opt NULL or all zero: the reference's view -- every key point with a track is a disc of r^2 = 10 in CV_RGB(255,255,0) = BGR (0,255,255),
+ *     centred on its position truncated to int;
+ *   color_mode 1: by age -- age < 4 BGR (0,0,255), 4 <= age < 10 (0,255,255), age >= 10 (0,255,0);
+ *   draw_new: key points without a track as discs of r^2 = 2 in BGR (255,255,0), below the tracked ones;
+ *   trail > 0: per tracked key point a polyline in BGR (255,160,0) from its position through its first min(trail, n_trail) trail positions
+ *     (needs XRSLAMAmdSetFeatureHistory); all lines lie below all discs.
+ * Deviation: the reference paints on the frame as pushed (in colour if it was); here the colour is gone after the upload and the canvas is
+ * the gray plane the tracker works on (after colour reduction and device undistortion, before CLAHE), replicated to B = G = R.
+ * Returns 1 on success; 0 with XRSLAMAmdLastError set when no frame has been tracked yet or the newest frame's plane is gone.  In
+ * pipelined mode the call does not wait for the backend.  The frame's plane is valid until the next frame is tracked. */
+typedef struct XRSLAMAmdViewOptions {
+    int color_mode;
+    int draw_new;
+    int trail;
+} XRSLAMAmdViewOptions;
+int XRSLAMAmdRenderTrackingView(void *out, int stride, int channels, int on_device, const XRSLAMAmdViewOptions *opt);
+
 /* ---- instance-scoped entry points (additive) ----
  * The six reference symbols above act on one process-global instance, like the reference's XRSLAMManager singleton
  * (xrslam-interface/src/XRSLAMManager.cpp:6-9).  The reference cannot do otherwise -- solver configuration, CLAHE /
@@ -258,6 +297,10 @@ void XRSLAMAmdInstanceGetInitReport(XRSLAMAmdInstance *inst, XRSLAMAmdInitReport
 const char *XRSLAMAmdInstanceLastError(XRSLAMAmdInstance *inst);
 void XRSLAMAmdInstanceSetThreading(XRSLAMAmdInstance *inst, int mode);
 void XRSLAMAmdInstanceFlush(XRSLAMAmdInstance *inst);
+int XRSLAMAmdInstanceGetFeatures(XRSLAMAmdInstance *inst, XRSLAMAmdFeature *out, int cap, double *timestamp);
+void XRSLAMAmdInstanceSetFeatureHistory(XRSLAMAmdInstance *inst, int frames);
+int XRSLAMAmdInstanceRenderTrackingView(XRSLAMAmdInstance *inst, void *out, int stride, int channels, int on_device,
+                                        const XRSLAMAmdViewOptions *opt);
 /* ---- instance groups (additive) ----
  * S independent sequences on one GPU leave it waiting on its own front end: every sequence issues ~26 small dependent launches per
  * frame.  Instances that have joined a group keep their state, ids and results to themselves but share launches: the library issues

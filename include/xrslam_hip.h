@@ -62,7 +62,8 @@ typedef struct xrhip_image xrhip_image;
 #define XRHIP_KLT_LEVELS 4   /* OpenCvImage::level_num()==3 -> maxLevel 3 -> 4 levels (opencv_image.h:20) */
 #define XRHIP_KLT_WIN 21     /* Size(21,21)            (opencv_image.cpp:96,122,159) */
 
-/* replaces: OpenCvImage::OpenCvImage + static clahe()/gftt() objects. */
+/* replaces: OpenCvImage::OpenCvImage + static clahe()/gftt() objects.  width, height >= 32; the tracker (xrhip_image_preprocess and
+ * what follows it) needs 64 a side, smaller frames can be uploaded and viewed (xrhip_image_render_view) only. */
 int xrhip_klt_create(int width, int height, int max_points, xrhip_klt **out);
 void xrhip_klt_destroy(xrhip_klt *ctx);
 
@@ -102,6 +103,38 @@ int xrhip_debug_get_raw(xrhip_image *img, uint8_t *out);
 int xrhip_debug_set_fused_pyramid(xrhip_klt *ctx, int on);
 int xrhip_debug_get_level_padded(const xrhip_image *img, int level, uint8_t *out, int *rows, int *cols);
 void xrhip_image_destroy(xrhip_image *img);
+
+/* Tracking view.  replaces: the InspectPainter a host registers in the feature_tracker_painter slot (xrslam-pc/player/src/main.cpp:110-113)
+ * and FeatureTracker::work paints the tracked key points with (core/feature_tracker.cpp:137-149): line segments and discs drawn over a
+ * frame, on the device, where the plane the tracker works on lives.  All integer; tests/view_model.py restates it in plain loops.
+ *   canvas   the frame's 8-bit gray plane as xrhip_image_preprocess reads it (after colour reduction and device undistortion, before CLAHE;
+ *            xrhip_debug_get_raw), replicated to B = G = R; with channels 4 the fourth byte is 255
+ *   segment  n = max(|x1-x0|, |y1-y0|); for k = 0..n the pixel x0 + floor((2 k (x1-x0) + n) / (2 n)), y likewise (floor division, not
+ *            truncation); n = 0 is the single pixel (x0, y0).  style = palette index
+ *   marker   every pixel with dx^2 + dy^2 <= r2 (r2 = 10: 37 pixels, r2 = 2: 9).  style = palette index | r2 << 8
+ *   clipping pixels outside the image are dropped; primitives may lie partly or wholly outside
+ *   priority any marker lies above any segment above the canvas; among markers, and among segments, the one LATER in its list wins --
+ *            whatever order the device runs them in
+ *   output   interleaved 8-bit BGR (channels 3) or BGRA (4) rows of stride_bytes >= width * channels (the bytes between rows are not
+ *            written), any base alignment: a host pointer, or an HBM pointer when on_device
+ * A host destination is complete when the call returns.  An HBM destination is written in stream order on the context's stream: it is
+ * complete after xrhip_klt_synchronize (or any later call on the context that waits for its stream), and must stay valid until then --
+ * as `gray_dev` of xrhip_image_upload_device.  (For a member of a group the call returns with the HBM destination complete.)
+ * A member of a group whose frame upload is still waiting for the group's shared launch submits that upload first; the render itself is
+ * not part of the group's launches (the member's own stream, after what it has queued on the plane).  The scratch of the view -- an owner
+ * word and four output bytes per pixel -- is allocated by the first render of a context: a context that never renders pays nothing.
+ * XRHIP_EINVAL: a null pointer, channels other than 3 or 4, stride_bytes < width * channels, n_palette > 256, a palette index >=
+ * n_palette, a coordinate outside [-8192, 8191] (2 k d + n stays inside 32 bits), more than 2^22 primitives in a list.
+ * XRHIP_ESTATE: the image has no valid gray plane (after xrhip_image_release, or never uploaded); a stale plane is never read. */
+typedef struct xrhip_view_marker { int32_t x, y; uint32_t style; } xrhip_view_marker;
+typedef struct xrhip_view_segment { int32_t x0, y0, x1, y1; uint32_t style; } xrhip_view_segment;
+int xrhip_image_render_view(xrhip_image *img, const xrhip_view_segment *segs, int n_segs,
+                            const xrhip_view_marker *markers, int n_markers,
+                            const uint8_t *palette_bgr, int n_palette,
+                            void *out, int stride_bytes, int channels, int on_device);
+/* measurement aid: with enable = 1 every render of the context is timed with HIP events on its stream (clear, stamp, compose, the copy
+ * to a host destination) and waited for; ms_sum / n (may be NULL) return the sum and the count so far.  enable < 0 leaves the switch. */
+int xrhip_debug_view_timing(xrhip_klt *ctx, int enable, double *ms_sum, long long *n, int reset);
 
 /* replaces: Image::preprocess(clipLimit, width, height)  (xrslam.h:153,
  * opencv_image.cpp:156-161): CLAHE in place + 4-level LK pyramid with Scharr

@@ -50,6 +50,9 @@
 extern "C" {
 int xrhip_image_upload_color(xrhip_image *img, const void *pixels, int stride_bytes, int channels, int on_device) __attribute__((weak));
 int xrhip_image_upload_color_distorted(xrhip_image *img, const void *pixels, int stride_bytes, int channels, int on_device) __attribute__((weak));
+// (likewise the tracking view's renderer: the feature snapshot below needs nothing of it)
+int xrhip_image_render_view(xrhip_image *img, const xrhip_view_segment *segs, int n_segs, const xrhip_view_marker *markers, int n_markers,
+                            const uint8_t *palette_bgr, int n_palette, void *out, int stride_bytes, int channels, int on_device) __attribute__((weak));
 }
 
 namespace xrh {
@@ -2780,6 +2783,7 @@ class System {   // XRSLAM::Detail + FeatureTracker + FrontendWorker: inline, or
             sync();
         } catch (...) {
         }
+        view.image.reset();   // (the snapshot's frame returns its buffer to the pool while `P` is alive)
         worker.reset();
         try {   // the launches of the last marginalisation read the prior's arrays, which die with `swt` (before `P`)
             P.marg_launch_wait();
@@ -3186,6 +3190,7 @@ class System {   // XRSLAM::Detail + FeatureTracker + FrontendWorker: inline, or
         if (swt_tag) frontend_work(map->get_frame(map->frame_num() - 1)->id, overlap_detect ? attached : nullptr, std::move(deferred_tag));
         // XRSLAM_AMD_DUMP_OUT: the 'F' record (ba_dump.hpp) -- the key points this frame carries out of the tracker (tracked and newly detected, in
         // key-point order) and the tracks they are on (new tracks are created when the NEXT frame continues a point)
+        snapshot_features(map, attached);
         if (P.out_log.enabled()) {
             OutLogger::Record r(P.out_log, 'F');
             r.u64(attached->id);
@@ -3196,6 +3201,60 @@ class System {   // XRSLAM::Detail + FeatureTracker + FrontendWorker: inline, or
                 r.f64(px.x);
                 r.f64(px.y);
                 r.i64(attached->get_track(k) ? (int64_t)attached->get_track(k)->id : -1);
+            }
+        }
+    }
+
+    // -------- the tracker's view of its newest frame (replaces: the feature_tracker_painter slot, core/feature_tracker.cpp:137-149)
+    // What the 'F' record of the output log holds, kept for the getters (XRSLAM_RESULT_FEATURES, XRSLAMAmdGetFeatures) and the rendered
+    // view: per key point of the tracking map's newest frame, in key-point order, its pixel position (the 'F' record's expression and
+    // bits), its track's id (-1: none) and key-point count in the tracking map (what Frame::track_keypoints sorts by), and -- while
+    // view_history > 0 -- where the same track was in the frames before, newest first, up to the first frame that does not have it.
+    // The frame's image stays referenced: its plane is valid until the next frame's tracking releases it.
+    static constexpr int VIEW_MAX_TRAIL = 8;   // XRSLAM_AMD_VIEW_MAX_TRAIL
+    struct ViewFeature {
+        double x, y;
+        long long track_id;
+        int age, n_trail;
+        double trail[VIEW_MAX_TRAIL][2];
+    };
+    struct ViewSnapshot {
+        bool valid = false;
+        size_t frame_id = 0;
+        double t = 0;
+        std::shared_ptr<HipImage> image;
+        std::vector<ViewFeature> features;
+    };
+    std::mutex view_mutex;   // the getters may be called while a frame is tracked (the pipelined backend never touches the snapshot)
+    ViewSnapshot view;
+    std::atomic<int> view_history{0};
+    void snapshot_features(const Map *map, const Frame *newest) {
+        std::lock_guard<std::mutex> lk(view_mutex);
+        const int history = std::min(view_history.load(std::memory_order_relaxed), VIEW_MAX_TRAIL);
+        const size_t nf = map->frame_num();
+        view.valid = true;
+        view.frame_id = newest->id;
+        view.t = newest->image->t;
+        view.image = newest->image;
+        view.features.resize(newest->keypoint_num());
+        for (size_t k = 0; k < newest->keypoint_num(); ++k) {
+            ViewFeature &f = view.features[k];
+            const V2 px = apply_k(newest->get_keypoint(k), newest->K);
+            Track *const tr = newest->get_track(k);
+            f.x = px.x;
+            f.y = px.y;
+            f.track_id = tr ? (long long)tr->id : -1;
+            f.age = tr ? (int)tr->keypoint_num() : 0;
+            f.n_trail = 0;
+            if (!tr || history <= 0 || nf < 2 || map->get_frame(nf - 1) != newest) continue;
+            for (size_t j = nf - 1; j-- > 0 && f.n_trail < history;) {
+                Frame *const fj = map->get_frame(j);
+                const size_t kj = tr->get_keypoint_index(fj);
+                if (kj == nil()) break;
+                const V2 pj = apply_k(fj->get_keypoint(kj), fj->K);
+                f.trail[f.n_trail][0] = pj.x;
+                f.trail[f.n_trail][1] = pj.y;
+                ++f.n_trail;
             }
         }
     }

@@ -167,6 +167,14 @@ void impl_get_result(Manager &m, XRSLAMResultType type, void *out) {
             }
             break;
         }
+        case XRSLAM_RESULT_FEATURES: {   // the painter's set (core/feature_tracker.cpp:143): key points with a track, in key-point order
+            auto *ft = static_cast<XRSLAMFeatures *>(out);
+            ft->pos.clear();
+            std::lock_guard<std::mutex> lk(m.sys->view_mutex);
+            for (const auto &f : m.sys->view.features)
+                if (f.track_id >= 0) ft->pos.push_back({f.x, f.y});
+            break;
+        }
         case XRSLAM_RESULT_BIAS: {
             auto *b = static_cast<XRSLAMIMUBias *>(out);
             m.sys->sync();
@@ -339,6 +347,66 @@ void impl_get_klt_stats(Manager &m, void *out, int reset) {
     guarded(m, [&] { xrh::hip_check(xrhip_klt_get_stats(m.sys->P.klt, static_cast<xrhip_klt_stats *>(out), reset), "xrhip_klt_get_stats"); });
 }
 
+static_assert(sizeof(XRSLAMAmdFeature) == sizeof(xrh::System::ViewFeature) && XRSLAM_AMD_VIEW_MAX_TRAIL == xrh::System::VIEW_MAX_TRAIL,
+              "XRSLAMAmdFeature is the snapshot's record");
+
+int impl_get_features(Manager &m, XRSLAMAmdFeature *out, int cap, double *timestamp) {
+    if (!m.sys) return 0;
+    std::lock_guard<std::mutex> lk(m.sys->view_mutex);
+    const auto &v = m.sys->view;
+    if (!v.valid) return 0;
+    if (timestamp) *timestamp = v.t;
+    const int n = (int)v.features.size();
+    if (out && cap > 0) std::memcpy(out, v.features.data(), sizeof(XRSLAMAmdFeature) * (size_t)std::min(n, cap));
+    return n;
+}
+
+void impl_set_feature_history(Manager &m, int frames) {
+    if (m.sys) m.sys->view_history.store(std::max(0, std::min(frames, (int)XRSLAM_AMD_VIEW_MAX_TRAIL)), std::memory_order_relaxed);
+}
+
+// palette of the tracking view: the reference's yellow, the three ages, the new key points, the trails
+const uint8_t kViewPalette[6][3] = {{0, 255, 255}, {0, 0, 255}, {0, 255, 255}, {0, 255, 0}, {255, 255, 0}, {255, 160, 0}};
+
+// (a view that cannot be drawn is reported, not recovered from: nothing of the pipeline was touched)
+int impl_render_view(Manager &m, void *out, int stride, int channels, int on_device, const XRSLAMAmdViewOptions *opt) {
+    if (!m.sys) return 0;
+    bind_device(m);
+    try {
+        if (!xrhip_image_render_view) throw std::runtime_error("this library has no view renderer");
+        const XRSLAMAmdViewOptions o = opt ? *opt : XRSLAMAmdViewOptions{0, 0, 0};
+        std::lock_guard<std::mutex> lk(m.sys->view_mutex);
+        const auto &v = m.sys->view;
+        if (!v.valid) throw std::runtime_error("no frame has been tracked yet");
+        if (!v.image || !v.image->h) throw std::runtime_error("the newest frame's image has been released");
+        std::vector<xrhip_view_marker> markers;
+        std::vector<xrhip_view_segment> segs;
+        markers.reserve(v.features.size());
+        if (o.draw_new)
+            for (const auto &f : v.features)
+                if (f.track_id < 0) markers.push_back({(int32_t)f.x, (int32_t)f.y, 4u | (2u << 8)});
+        for (const auto &f : v.features) {
+            if (f.track_id < 0) continue;
+            const uint32_t pal = o.color_mode == 1 ? (f.age < 4 ? 1u : f.age < 10 ? 2u : 3u) : 0u;
+            markers.push_back({(int32_t)f.x, (int32_t)f.y, pal | (10u << 8)});
+            int px = (int32_t)f.x, py = (int32_t)f.y;
+            for (int j = 0; j < std::min(o.trail, f.n_trail); ++j) {
+                const int qx = (int32_t)f.trail[j][0], qy = (int32_t)f.trail[j][1];
+                segs.push_back({px, py, qx, qy, 5u});
+                px = qx;
+                py = qy;
+            }
+        }
+        xrh::hip_check(xrhip_image_render_view(v.image->h, segs.data(), (int)segs.size(), markers.data(), (int)markers.size(),
+                                               &kViewPalette[0][0], 6, out, stride, channels, on_device),
+                       "xrhip_image_render_view");
+        return 1;
+    } catch (const std::exception &e) {
+        m.last_error = std::string("XRSLAMAmdRenderTrackingView: ") + e.what();
+        return 0;
+    }
+}
+
 void impl_get_init_report(Manager &m, XRSLAMAmdInitReport *out) {
     if (!m.sys || !out) return;
     const xrh::Initializer &in = m.sys->init;
@@ -399,6 +467,11 @@ void XRSLAMAmdGetInitReport(XRSLAMAmdInitReport *out) { impl_get_init_report(mgr
 const char *XRSLAMAmdLastError(void) { return mgr().last_error.c_str(); }
 void XRSLAMAmdSetThreading(int mode) { impl_set_threading(mgr(), mode); }
 void XRSLAMAmdFlush(void) { impl_flush(mgr()); }
+int XRSLAMAmdGetFeatures(XRSLAMAmdFeature *out, int cap, double *timestamp) { return impl_get_features(mgr(), out, cap, timestamp); }
+void XRSLAMAmdSetFeatureHistory(int frames) { impl_set_feature_history(mgr(), frames); }
+int XRSLAMAmdRenderTrackingView(void *out, int stride, int channels, int on_device, const XRSLAMAmdViewOptions *opt) {
+    return impl_render_view(mgr(), out, stride, channels, on_device, opt);
+}
 
 // ---- the same entry points on caller-owned instances (several sequences per process / per GPU)
 int XRSLAMAmdInstanceCreate(const char *slam_config_path, const char *device_config_path, XRSLAMAmdInstance **out,
@@ -471,6 +544,17 @@ void XRSLAMAmdInstanceSetThreading(XRSLAMAmdInstance *inst, int mode) {
 }
 void XRSLAMAmdInstanceFlush(XRSLAMAmdInstance *inst) {
     if (inst) impl_flush(inst->m);
+}
+
+int XRSLAMAmdInstanceGetFeatures(XRSLAMAmdInstance *inst, XRSLAMAmdFeature *out, int cap, double *timestamp) {
+    return inst ? impl_get_features(inst->m, out, cap, timestamp) : 0;
+}
+void XRSLAMAmdInstanceSetFeatureHistory(XRSLAMAmdInstance *inst, int frames) {
+    if (inst) impl_set_feature_history(inst->m, frames);
+}
+int XRSLAMAmdInstanceRenderTrackingView(XRSLAMAmdInstance *inst, void *out, int stride, int channels, int on_device,
+                                        const XRSLAMAmdViewOptions *opt) {
+    return inst ? impl_render_view(inst->m, out, stride, channels, on_device, opt) : 0;
 }
 
 // ---- instance groups

@@ -122,6 +122,17 @@ struct xrhip_klt {
     std::vector<Pending> pending;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
     xrhip_klt_stats stats{};
+    // tracking view (xrhip_image_render_view): nothing of it exists before the first render of this context
+    uint32_t *view_owner = nullptr;   // w*h owner words
+    uint8_t *view_out = nullptr;      // w*h*4: the rendered rows on their way to a host destination
+    char *view_stage = nullptr;       // pinned, device-mapped: segments | markers | palette of the render in flight
+    size_t view_stage_cap = 0;
+    hipEvent_t view_done = nullptr;   // the last render has read the staging block
+    bool view_busy = false;
+    hipEvent_t view_t0 = nullptr, view_t1 = nullptr;   // xrhip_debug_view_timing
+    bool view_timing = false;
+    double view_ms = 0;
+    long long view_n = 0;
 };
 
 struct xrhip_image {
@@ -455,7 +466,8 @@ int xrhip_klt_group_busy(xrhip_klt *c, int busy) {
 }
 
 int xrhip_klt_create(int width, int height, int max_points, xrhip_klt **out) {
-    if (!out || width < 64 || height < 64 || max_points < 0) return xr_fail(XRHIP_EINVAL, "xrhip_klt_create: bad arguments");
+    // (the tracker wants 64 pixels a side -- xrhip_image_preprocess; a frame of 32 can still be uploaded and viewed)
+    if (!out || width < 32 || height < 32 || max_points < 0) return xr_fail(XRHIP_EINVAL, "xrhip_klt_create: bad arguments");
     int rc = xr_require_device();
     if (rc) return rc;
     xrhip_klt *c = new xrhip_klt();
@@ -527,6 +539,12 @@ void xrhip_klt_destroy(xrhip_klt *c) {
     hipFree(c->d_fnext);
     hipFree(c->d_counters);
     hipHostFree(c->h_counters);
+    hipFree(c->view_owner);
+    hipFree(c->view_out);
+    hipHostFree(c->view_stage);
+    if (c->view_done) hipEventDestroy(c->view_done);
+    if (c->view_t0) hipEventDestroy(c->view_t0);
+    if (c->view_t1) hipEventDestroy(c->view_t1);
     for (int i = 0; i < xrhip_klt::UP_SLOTS; ++i) {
         hipHostFree(c->up_buf[i]);
         if (c->up_done[i]) hipEventDestroy(c->up_done[i]);
@@ -868,6 +886,7 @@ int xrhip_image_preprocess(xrhip_image *im, double clip_limit, int tiles_x, int 
     if (!im->have_raw) return xr_fail(XRHIP_ESTATE, "xrhip_image_preprocess: no image uploaded");
     xrhip_klt *c = im->ctx;
     const int w = c->w, h = c->h;
+    if (w < 64 || h < 64) return xr_fail(XRHIP_EINVAL, "xrhip_image_preprocess: the tracker needs at least 64 pixels a side");
     const int ew = w + (tiles_x - (w % tiles_x)) % tiles_x, eh = h + (tiles_y - (h % tiles_y)) % tiles_y;
     const int tw = ew / tiles_x, th = eh / tiles_y;
     const int tiles = tiles_x * tiles_y;
@@ -1305,6 +1324,120 @@ int xrhip_klt_get_stats(xrhip_klt *c, xrhip_klt_stats *out, int reset) {
             return XRHIP_OK;
         });
         if (rc) return rc;
+    }
+    return XRHIP_OK;
+}
+
+// The tracking view of a frame: segments and markers over its gray plane (include/xrslam_hip.h has the semantics).  Three steps on the
+// context's OWN stream -- clear the owner plane, k_view_stamp, k_view_compose -- behind whatever the context still has queued on the
+// plane: a member of a group submits a pending upload, waits for its requests on the group's queue and renders then.
+int xrhip_image_render_view(xrhip_image *im, const xrhip_view_segment *segs, int n_segs, const xrhip_view_marker *markers, int n_markers,
+                            const uint8_t *palette_bgr, int n_palette, void *out, int stride, int channels, int on_device) {
+    if (!im || !out || (n_segs > 0 && !segs) || (n_markers > 0 && !markers) || (n_palette > 0 && !palette_bgr))
+        return xr_fail(XRHIP_EINVAL, "xrhip_image_render_view: null argument");
+    if (channels != 3 && channels != 4) return xr_fail(XRHIP_EINVAL, "xrhip_image_render_view: channels must be 3 (BGR) or 4 (BGRA)");
+    xrhip_klt *c = im->ctx;
+    if ((long long)stride < (long long)c->w * channels) return xr_fail(XRHIP_EINVAL, "xrhip_image_render_view: stride_bytes < width * channels");
+    if (n_segs < 0 || n_markers < 0 || n_palette < 0 || n_palette > 256 || n_segs > VIEW_MAX_PRIMS || n_markers > VIEW_MAX_PRIMS)
+        return xr_fail(XRHIP_EINVAL, "xrhip_image_render_view: bad primitive or palette count");
+    auto coord_ok = [](int v) { return v >= -VIEW_COORD_MAX - 1 && v <= VIEW_COORD_MAX; };
+    for (int i = 0; i < n_segs; ++i) {
+        const xrhip_view_segment &s = segs[i];
+        if (!coord_ok(s.x0) || !coord_ok(s.y0) || !coord_ok(s.x1) || !coord_ok(s.y1))
+            return xr_fail(XRHIP_EINVAL, "xrhip_image_render_view: segment coordinate outside [-8192, 8191]");
+        if (s.style >= (uint32_t)n_palette) return xr_fail(XRHIP_EINVAL, "xrhip_image_render_view: segment palette index >= n_palette");
+    }
+    for (int i = 0; i < n_markers; ++i) {
+        const xrhip_view_marker &m = markers[i];
+        if (!coord_ok(m.x) || !coord_ok(m.y)) return xr_fail(XRHIP_EINVAL, "xrhip_image_render_view: marker coordinate outside [-8192, 8191]");
+        if ((m.style & 255u) >= (uint32_t)n_palette) return xr_fail(XRHIP_EINVAL, "xrhip_image_render_view: marker palette index >= n_palette");
+    }
+    if (!im->have_raw) return xr_fail(XRHIP_ESTATE, "xrhip_image_render_view: the image has no gray plane (released, or never uploaded)");
+    static_assert(sizeof(xrhip_view_segment) == sizeof(ViewSeg) && sizeof(xrhip_view_marker) == sizeof(ViewMarker), "view primitives");
+    const int w = c->w, h = c->h;
+    // scratch of the view: allocated by the first render of the context
+    if (!c->view_owner) {
+        XR_HIP(hipMalloc(&c->view_owner, sizeof(uint32_t) * (size_t)w * h));
+        XR_HIP(hipMalloc(&c->view_out, (size_t)w * h * 4));
+        XR_HIP(hipEventCreateWithFlags(&c->view_done, hipEventDisableTiming));
+    }
+    if (c->view_busy) {   // (an HBM render still reading the staging block)
+        XR_HIP(hipEventSynchronize(c->view_done));
+        c->view_busy = false;
+    }
+    const size_t seg_bytes = sizeof(ViewSeg) * (size_t)n_segs, mk_bytes = sizeof(ViewMarker) * (size_t)n_markers;
+    const size_t pal_off = (seg_bytes + mk_bytes + 15) & ~(size_t)15, need = pal_off + 768;
+    if (need > c->view_stage_cap) {
+        hipHostFree(c->view_stage);
+        c->view_stage = nullptr;
+        c->view_stage_cap = 0;
+        const size_t cap = std::max(need, (size_t)16384);
+        XR_HIP(hipHostMalloc(&c->view_stage, cap, hipHostMallocDefault));
+        c->view_stage_cap = cap;
+    }
+    if (seg_bytes) std::memcpy(c->view_stage, segs, seg_bytes);
+    if (mk_bytes) std::memcpy(c->view_stage + seg_bytes, markers, mk_bytes);
+    std::memset(c->view_stage + pal_off, 0, 768);
+    if (n_palette) std::memcpy(c->view_stage + pal_off, palette_bgr, 3 * (size_t)n_palette);
+    char *dstage = nullptr;
+    XR_HIP(hipHostGetDevicePointer((void **)&dstage, c->view_stage, 0));
+    // everything this context has queued on the plane comes first
+    int rc = flush_upload(c);
+    if (rc) return rc;
+    if (c->group) {
+        rc = group_drain(c->group, GQ_KLT, c);
+        if (rc) return rc;
+        c->uploads_unsynced = 0;
+    }
+    hipStream_t st = c->stream;
+    if (c->view_timing) {
+        if (!c->view_t0) {
+            XR_HIP(hipEventCreate(&c->view_t0));
+            XR_HIP(hipEventCreate(&c->view_t1));
+        }
+        XR_HIP(hipEventRecord(c->view_t0, st));
+    }
+    const int prims = n_segs + n_markers;
+    uint8_t *target = on_device ? static_cast<uint8_t *>(out) : c->view_out;
+    const int tstride = on_device ? stride : w * channels;
+    XR_HIP(hipMemsetAsync(c->view_owner, 0, sizeof(uint32_t) * (size_t)w * h, st));
+    if (prims)
+        hipLaunchKernelGGL(k_view_stamp, dim3((prims + 3) / 4), dim3(256), 0, st, reinterpret_cast<const ViewSeg *>(dstage), n_segs,
+                           reinterpret_cast<const ViewMarker *>(dstage + seg_bytes), n_markers, c->view_owner, w, h);
+    {
+        const unsigned groups = (unsigned)((w + 3) / 4) * (unsigned)h;
+        hipLaunchKernelGGL(k_view_compose, dim3(std::max(1u, std::min((groups + 255u) / 256u, 1024u))), dim3(256), 0, st, im->raw, c->view_owner,
+                           reinterpret_cast<const uint8_t *>(dstage + pal_off), target, tstride, w, h, channels);
+    }
+    XR_HIP(hipGetLastError());
+    if (!on_device) XR_HIP(hipMemcpy2DAsync(out, (size_t)stride, c->view_out, (size_t)tstride, (size_t)w * channels, (size_t)h, hipMemcpyDeviceToHost, st));
+    if (c->view_timing) XR_HIP(hipEventRecord(c->view_t1, st));
+    if (!on_device || c->group || c->view_timing) {
+        // a host destination is complete on return; so is a group member's HBM destination (its later uploads travel on the group's
+        // queue, which this stream does not order)
+        XR_HIP(hipStreamSynchronize(st));
+        if (c->view_timing) {
+            float ms = 0.f;
+            XR_HIP(hipEventElapsedTime(&ms, c->view_t0, c->view_t1));
+            c->view_ms += ms;
+            c->view_n++;
+        }
+    } else {
+        XR_HIP(hipEventRecord(c->view_done, st));
+        c->view_busy = true;
+    }
+    return XRHIP_OK;
+}
+
+/* measurement aid: HIP-event time of the renders of this context, first to last command (enable < 0: leave the switch alone) */
+int xrhip_debug_view_timing(xrhip_klt *c, int enable, double *ms_sum, long long *n, int reset) {
+    if (!c) return xr_fail(XRHIP_EINVAL, "xrhip_debug_view_timing: null");
+    if (enable >= 0) c->view_timing = enable != 0;
+    if (ms_sum) *ms_sum = c->view_ms;
+    if (n) *n = c->view_n;
+    if (reset) {
+        c->view_ms = 0;
+        c->view_n = 0;
     }
     return XRHIP_OK;
 }

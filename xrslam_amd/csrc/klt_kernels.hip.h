@@ -1495,6 +1495,123 @@ __global__ __launch_bounds__(256) void k_upload(Batch<UploadArgs> b) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------- tracking view (xrhip_image_render_view)
+// Line segments and discs over a frame's gray plane, all in integers.  Which primitive a pixel shows must not depend on how the GPU
+// schedules the lanes: k_view_stamp takes atomicMax of a word ordered like the priority rule into a 32-bit owner plane (cleared per
+// render), k_view_compose turns gray + owner into the BGR / BGRA rows.
+//   owner word: layer << 30 (2 marker, 1 segment, 0 canvas) | index in its list << 8 | palette index
+constexpr int VIEW_COORD_MAX = 8191;          // |coordinate| <= 8191 (+1 below): 2 k d + n of a segment stays inside 32 bits
+constexpr int VIEW_MAX_PRIMS = 1 << 22;       // 22 bits of list index
+struct ViewSeg {
+    int x0, y0, x1, y1;
+    uint32_t style;
+};
+struct ViewMarker {
+    int x, y;
+    uint32_t style;
+};
+__device__ __forceinline__ int view_floordiv(int a, int b) {   // b > 0
+    return a >= 0 ? a / b : -((-a + b - 1) / b);
+}
+// One wavefront per primitive (segments first, then markers), lanes across its pixels.
+__global__ __launch_bounds__(256) void k_view_stamp(const ViewSeg *__restrict__ segs, int n_segs, const ViewMarker *__restrict__ markers,
+                                                    int n_markers, uint32_t *__restrict__ owner, int w, int h) {
+    const int prim = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (prim < n_segs) {
+        const ViewSeg s = segs[prim];
+        const int dx = s.x1 - s.x0, dy = s.y1 - s.y0;
+        const int n = max(abs(dx), abs(dy));
+        const uint32_t word = (1u << 30) | ((uint32_t)prim << 8) | (s.style & 255u);
+        if (n == 0) {
+            if (lane == 0 && s.x0 >= 0 && s.x0 < w && s.y0 >= 0 && s.y0 < h) atomicMax(&owner[(size_t)s.y0 * w + s.x0], word);
+            return;
+        }
+        for (int k = lane; k <= n; k += 64) {
+            const int x = s.x0 + view_floordiv(2 * k * dx + n, 2 * n);
+            const int y = s.y0 + view_floordiv(2 * k * dy + n, 2 * n);
+            if (x >= 0 && x < w && y >= 0 && y < h) atomicMax(&owner[(size_t)y * w + x], word);
+        }
+        return;
+    }
+    const int mi = prim - n_segs;
+    if (mi >= n_markers) return;
+    const ViewMarker m = markers[mi];
+    const int r2 = (int)(m.style >> 8);
+    int r = (int)sqrtf((float)r2);
+    while (r * r > r2) --r;
+    while ((r + 1) * (r + 1) <= r2) ++r;
+    // the disc's bounding box, clipped to the image
+    const int bx0 = max(m.x - r, 0), bx1 = min(m.x + r, w - 1), by0 = max(m.y - r, 0), by1 = min(m.y + r, h - 1);
+    if (bx0 > bx1 || by0 > by1) return;
+    const int bw = bx1 - bx0 + 1, total = bw * (by1 - by0 + 1);
+    const uint32_t word = (2u << 30) | ((uint32_t)mi << 8) | (m.style & 255u);
+    for (int i = lane; i < total; i += 64) {
+        const int yy = i / bw;
+        const int x = bx0 + (i - yy * bw), y = by0 + yy;
+        const int ddx = x - m.x, ddy = y - m.y;
+        if (ddx * ddx + ddy * ddy <= r2) atomicMax(&owner[(size_t)y * w + x], word);
+    }
+}
+// A lane owns four consecutive pixels of one row: their gray bytes, their owner words, 12 / 16 output bytes.  Where the gray bytes
+// (the plane is dense, so rows of an odd width start anywhere) or the output bytes (any base, any stride) are not dword-aligned, and
+// for the last w % 4 pixels of a row, the lane goes byte by byte.
+template <int CH> __device__ __forceinline__ void view_pixel(uint32_t g, uint32_t o, const uint8_t *__restrict__ pal, uint8_t px[4]) {
+    if (o) {
+        const uint8_t *p = pal + 3u * (o & 255u);
+        px[0] = p[0];
+        px[1] = p[1];
+        px[2] = p[2];
+    } else {
+        px[0] = px[1] = px[2] = (uint8_t)g;
+    }
+    px[3] = 255;
+}
+template <int CH> __device__ __forceinline__ void d_view_compose(const uint8_t *__restrict__ gray, const uint32_t *__restrict__ owner,
+                                                                const uint8_t *__restrict__ pal, uint8_t *__restrict__ out, int stride,
+                                                                int w, int h) {
+    const uint32_t groups = ((uint32_t)w + 3u) >> 2, total = groups * (uint32_t)h;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+        const uint32_t y = i / groups, x = (i - y * groups) << 2;
+        const size_t p0 = (size_t)y * w + x;
+        uint8_t *dst = out + (size_t)y * (size_t)stride + (size_t)x * CH;
+        const uint32_t np = min(4u, (uint32_t)w - x);
+        uint32_t g[4] = {0, 0, 0, 0};
+        if (np == 4 && (reinterpret_cast<uintptr_t>(gray + p0) & 3) == 0) {
+            const uint32_t d = *reinterpret_cast<const uint32_t *>(gray + p0);
+            g[0] = d & 255u;
+            g[1] = (d >> 8) & 255u;
+            g[2] = (d >> 16) & 255u;
+            g[3] = d >> 24;
+        } else {
+            for (uint32_t k = 0; k < np; ++k) g[k] = gray[p0 + k];
+        }
+        uint8_t px[4][4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) view_pixel<CH>(g[k], k < np ? owner[p0 + k] : 0u, pal, px[k]);
+        if (np == 4 && (reinterpret_cast<uintptr_t>(dst) & 3) == 0) {
+            uint32_t *d4 = reinterpret_cast<uint32_t *>(dst);
+            if (CH == 4) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) d4[k] = px[k][0] | (px[k][1] << 8) | (px[k][2] << 16) | (255u << 24);
+            } else {
+                d4[0] = px[0][0] | (px[0][1] << 8) | (px[0][2] << 16) | ((uint32_t)px[1][0] << 24);
+                d4[1] = px[1][1] | (px[1][2] << 8) | (px[2][0] << 16) | ((uint32_t)px[2][1] << 24);
+                d4[2] = px[2][2] | (px[3][0] << 8) | (px[3][1] << 16) | ((uint32_t)px[3][2] << 24);
+            }
+        } else {
+            for (uint32_t k = 0; k < np; ++k)
+                for (int ch = 0; ch < CH; ++ch) dst[k * CH + ch] = px[k][ch];
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_view_compose(const uint8_t *__restrict__ gray, const uint32_t *__restrict__ owner,
+                                                      const uint8_t *__restrict__ pal, uint8_t *__restrict__ out, int stride, int w,
+                                                      int h, int channels) {
+    if (channels == 4) d_view_compose<4>(gray, owner, pal, out, stride, w, h);
+    else d_view_compose<3>(gray, owner, pal, out, stride, w, h);
+}
+
 // plain calcOpticalFlowPyrLK (float in/out, every point) -- parity aid
 __global__ __launch_bounds__(LK_THREADS) void k_lk_plain(PyrView A, PyrView B, const float2 *__restrict__ prev,
                                                  float2 *__restrict__ next_io, uint8_t *__restrict__ status_out,

@@ -23,12 +23,15 @@
 // By default the library initialises itself (SfM + IMU alignment, like the reference).  With --bootstrap-frames N
 // the first N camera frames are instead seeded from state_groundtruth_estimate0 through XRSLAMAmdSetInitialState
 // (N >= 36 covers the first window), which takes the initialiser out of an accuracy / throughput comparison.
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "XRSLAM.h"
 #include "euroc_io.hpp"
@@ -84,6 +87,7 @@ int main(int argc, char **argv) {
     if (!opt.count("slam") || !opt.count("device") || !opt.count("euroc")) {
         std::fprintf(stderr, "usage: xrslam-player --slam cfg.yaml --device sensor.yaml --euroc <dir>/mav0 [--out traj.tum] "
                              "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color]\n"
+                             "       [--view-out DIR [--view-every N] [--view-mode reference|age] [--view-trail K]]\n"
                              "   or: xrslam-player -sc cfg.yaml -dc sensor.yaml [--tum traj.tum] [--csv traj.csv] [-p] "
                              "euroc://<dir>/mav0 | tum://<dir>/mav0\n");
         return 2;
@@ -135,6 +139,46 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "Cannot open file\n");   // trajectory_writer.h:37,62
         return 1;
     }
+    // --view-out DIR: the tracker's view of every N-th tracked frame (XRSLAMAmdRenderTrackingView: the reference player's
+    // feature_tracker_painter window, main.cpp:110-113) as DIR/<timestamp in ns>.ppm -- binary P6, RGB
+    const bool view_on = opt.count("view-out") != 0;
+    const long view_every = opt.count("view-every") ? std::max(1L, std::atol(opt["view-every"].c_str())) : 1;
+    XRSLAMAmdViewOptions view_opt = {0, 0, 0};
+    if (opt.count("view-mode")) {
+        if (opt["view-mode"] == "age") view_opt.color_mode = 1, view_opt.draw_new = 1;
+        else if (opt["view-mode"] != "reference") {
+            std::fprintf(stderr, "--view-mode is reference or age\n");
+            return 2;
+        }
+    }
+    if (opt.count("view-trail")) view_opt.trail = (int)std::max(0L, std::min(8L, std::atol(opt["view-trail"].c_str())));
+    if (view_on && view_opt.trail > 0) XRSLAMAmdSetFeatureHistory(view_opt.trail);
+    long view_seen = 0, view_written = 0;
+    double view_last_t = -1.0;
+    std::vector<uint8_t> view_px;
+    auto write_view = [&]() -> bool {   // false: the run ends with the error
+        double t = 0.0;
+        if (!view_on || XRSLAMAmdGetFeatures(nullptr, 0, &t) <= 0 || t == view_last_t) return true;
+        view_last_t = t;
+        if (view_seen++ % view_every != 0) return true;
+        const int w = (int)cfg.cam_resolution[0], h = (int)cfg.cam_resolution[1];
+        view_px.resize((size_t)w * h * 3);
+        if (XRSLAMAmdRenderTrackingView(view_px.data(), w * 3, 3, 0, &view_opt) != 1) return false;
+        for (size_t i = 0; i < view_px.size(); i += 3) std::swap(view_px[i], view_px[i + 2]);   // BGR -> RGB
+        char name[64];
+        std::snprintf(name, sizeof(name), "/%lld.ppm", (long long)std::llround(t * 1e9));
+        FILE *fp = std::fopen((opt["view-out"] + name).c_str(), "wb");
+        if (!fp) {
+            std::fprintf(stderr, "Cannot open file\n");
+            return false;
+        }
+        std::fprintf(fp, "P6\n%d %d\n255\n", w, h);
+        const bool ok = std::fwrite(view_px.data(), 1, view_px.size(), fp) == view_px.size();
+        std::fclose(fp);
+        if (ok) ++view_written;
+        return ok;
+    };
+    bool view_failed = false;
     const double K4[4] = {cfg.K.fx, cfg.K.fy, cfg.K.cx, cfg.K.cy};
     std::unique_ptr<Undistorter> und;
     std::vector<uint8_t> rectified;
@@ -202,6 +246,10 @@ int main(int argc, char **argv) {
             XRSLAMPushSensorData(XRSLAM_SENSOR_CAMERA, &xi);
             if (has_gyro && has_acc) {
                 XRSLAMRunOneFrame();
+                if (!write_view()) {   // (the frame tracked since the last image: its plane lives until the next one is tracked)
+                    view_failed = true;
+                    break;
+                }
                 XRSLAMState state;
                 XRSLAMGetResult(XRSLAM_RESULT_STATE, &state);
                 if (state == XRSLAM_STATE_TRACKING_SUCCESS) {
@@ -228,14 +276,16 @@ int main(int argc, char **argv) {
     const double busy = std::chrono::duration<double>(std::chrono::steady_clock::now() - loop_begin).count() - io_seconds;
     if (out) std::fclose(out);
     if (csv) std::fclose(csv);
+    if (!view_failed && !write_view()) view_failed = true;
     const char *err = XRSLAMAmdLastError();
+    if (view_failed && !(err && *err)) err = "the tracking view could not be written";
     XRSLAMAmdInitReport rep;
     std::memset(&rep, 0, sizeof(rep));
     XRSLAMAmdGetInitReport(&rep);
     std::printf("{\"frames\": %zu, \"tracked\": %zu, \"bootstrap_states\": %zu, \"init_attempts\": %ld, \"init_scale\": %.6f, "
-                "\"ms_per_frame\": %.4f, \"io_ms_per_frame\": %.4f, \"ate_rmse_m\": %.6f, \"error\": \"%s\"}\n",
+                "\"ms_per_frame\": %.4f, \"io_ms_per_frame\": %.4f, \"ate_rmse_m\": %.6f, \"views\": %ld, \"error\": \"%s\"}\n",
                 frames, tracked, seeded, rep.attempts, rep.successes ? rep.scale : 0.0, frames ? 1e3 * busy / frames : 0.0,
-                frames ? 1e3 * io_seconds / frames : 0.0, est.size() >= 3 ? ate_rmse(est, ref) : -1.0, err ? err : "");
+                frames ? 1e3 * io_seconds / frames : 0.0, est.size() >= 3 ? ate_rmse(est, ref) : -1.0, view_written, err ? err : "");
     XRSLAMDestroy();
     return (err && *err) ? 1 : 0;
 }

@@ -38,6 +38,19 @@ class XRSLAMAmdTimes(C.Structure):
                 ("wall_frame", C.c_double), ("wall_scope", C.c_double * 16)]
 
 
+class XRSLAMAmdFeature(C.Structure):   # include/XRSLAM.h
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("track_id", C.c_longlong), ("age", C.c_int), ("n_trail", C.c_int),
+                ("trail", (C.c_double * 2) * 8)]
+
+
+class XRSLAMAmdViewOptions(C.Structure):
+    _fields_ = [("color_mode", C.c_int), ("draw_new", C.c_int), ("trail", C.c_int)]
+
+
+FEATURE_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("track_id", "<i8"), ("age", "<i4"), ("n_trail", "<i4"), ("trail", "<f8", (8, 2))])
+assert FEATURE_DTYPE.itemsize == C.sizeof(XRSLAMAmdFeature)
+
+
 class GroupStats(C.Structure):   # xrhip_group_stats (include/xrslam_hip.h)
     _fields_ = [("batches", C.c_longlong * 12), ("entries", C.c_longlong * 12), ("ms", C.c_double * 12), ("timed", C.c_longlong * 12)]
 
@@ -89,6 +102,12 @@ def load(lib_path):
     lib.XRSLAMAmdSetThreading.argtypes = [C.c_int]
     lib.XRSLAMAmdSetThreading.restype = None
     lib.XRSLAMAmdFlush.restype = None
+    have_view = hasattr(lib, "XRSLAMAmdRenderTrackingView")
+    if have_view:   # the tracking view (feature snapshot + rendered overlay)
+        lib.XRSLAMAmdGetFeatures.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+        lib.XRSLAMAmdSetFeatureHistory.argtypes = [C.c_int]
+        lib.XRSLAMAmdSetFeatureHistory.restype = None
+        lib.XRSLAMAmdRenderTrackingView.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(XRSLAMAmdViewOptions)]
     if hasattr(lib, "XRSLAMAmdInstanceCreate"):   # instance-scoped forms: the instance handle is the first argument
         H = C.c_void_p
         lib.XRSLAMAmdInstanceCreate.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(H), C.POINTER(C.c_void_p)]
@@ -104,6 +123,11 @@ def load(lib_path):
             fn = getattr(lib, "XRSLAMAmdInstance" + name)
             fn.argtypes = [H] + args
             fn.restype = res
+        if have_view:
+            lib.XRSLAMAmdInstanceGetFeatures.argtypes = [H, C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+            lib.XRSLAMAmdInstanceSetFeatureHistory.argtypes = [H, C.c_int]
+            lib.XRSLAMAmdInstanceSetFeatureHistory.restype = None
+            lib.XRSLAMAmdInstanceRenderTrackingView.argtypes = [H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(XRSLAMAmdViewOptions)]
         lib.XRSLAMAmdInstanceReplay.argtypes = [H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p]
         lib.XRSLAMAmdInstanceReplay.restype = C.c_int
@@ -173,6 +197,10 @@ class _Api:
                  "sync": ("XRSLAMAmdFlush", "XRSLAMAmdInstanceFlush")}
         if hasattr(lib, "XRSLAMAmdPushImageDeviceColor"):
             names["push_image_device_color"] = ("XRSLAMAmdPushImageDeviceColor", "XRSLAMAmdInstancePushImageDeviceColor")
+        if hasattr(lib, "XRSLAMAmdRenderTrackingView"):
+            names["get_features"] = ("XRSLAMAmdGetFeatures", "XRSLAMAmdInstanceGetFeatures")
+            names["set_feature_history"] = ("XRSLAMAmdSetFeatureHistory", "XRSLAMAmdInstanceSetFeatureHistory")
+            names["render_tracking_view"] = ("XRSLAMAmdRenderTrackingView", "XRSLAMAmdInstanceRenderTrackingView")
         for attr, (glob, inst) in names.items():
             setattr(self, attr, getattr(lib, glob) if handle is None else functools.partial(getattr(lib, inst), handle))
 
@@ -325,6 +353,33 @@ class Session:
         st = BaStats()
         self.api.get_ba_stats(C.byref(st), 1 if reset else 0)
         return st
+
+    def set_feature_history(self, frames):
+        """Trail history of the feature snapshot, 0 .. 8 frames (XRSLAMAmdSetFeatureHistory)"""
+        self.api.set_feature_history(int(frames))
+
+    def features(self):
+        """-> (timestamp, structured array FEATURE_DTYPE of all key points of the newest tracked frame), (None, empty) before it"""
+        t = C.c_double(0)
+        n = self.api.get_features(None, 0, C.byref(t))
+        out = np.zeros(n, FEATURE_DTYPE)
+        if n == 0:
+            return None, out
+        assert self.api.get_features(out.ctypes.data, n, C.byref(t)) == n
+        return t.value, out
+
+    def render_view(self, channels=3, color_mode=0, draw_new=0, trail=0, stride=None, out_dev=None):
+        """XRSLAMAmdRenderTrackingView -> uint8 [h][w][channels], or None when the library answers 0 (see error()); with out_dev (a
+        device pointer of rows `stride` bytes apart) the view stays in HBM and True is returned."""
+        h, w = self.seq["frames"].shape[1:3]
+        opt = XRSLAMAmdViewOptions(int(color_mode), int(draw_new), int(trail))
+        stride = w * channels if stride is None else int(stride)
+        if out_dev is not None:
+            return True if self.api.render_tracking_view(C.c_void_p(int(out_dev)), stride, channels, 1, C.byref(opt)) == 1 else None
+        buf = np.zeros(h * stride, np.uint8)
+        if self.api.render_tracking_view(buf.ctypes.data, stride, channels, 0, C.byref(opt)) != 1:
+            return None
+        return np.lib.stride_tricks.as_strided(buf, shape=(h, w, channels), strides=(stride, channels, 1))
 
     def init_report(self):
         r = XRSLAMAmdInitReport()

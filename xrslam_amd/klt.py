@@ -49,6 +49,8 @@ def _bind():
     L.xrhip_debug_get_raw.argtypes = [vp, vp]
     L.xrhip_debug_set_fused_pyramid.argtypes = [vp, C.c_int]
     L.xrhip_debug_get_level_padded.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.xrhip_image_render_view.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]
+    L.xrhip_debug_view_timing.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_int]
     return L
 
 
@@ -95,6 +97,12 @@ class KltContext:
 
     def synchronize(self):
         check(L().xrhip_klt_synchronize(self._h))
+
+    def view_timing(self, enable=-1, reset=False):
+        """HIP-event time of this context's renders (HipImage.render_view): -> (sum in ms, count); enable 1 / 0 switches it."""
+        ms, n = C.c_double(0), C.c_longlong(0)
+        check(L().xrhip_debug_view_timing(self._h, int(enable), C.byref(ms), C.byref(n), 1 if reset else 0))
+        return ms.value, n.value
 
     def set_fused_pyramid(self, on):
         """Development / parity switch: preprocess() builds the pyramid in one launch (default) or in the five it replaces."""
@@ -180,6 +188,31 @@ class HipImage:
         out = np.empty((self.ctx.h, self.ctx.w), np.uint8)
         check(L().xrhip_debug_get_raw(self._h, _p(out)))
         return out
+
+    def render_view(self, segments=(), markers=(), palette=(), channels=3, stride=None, out=None, on_device=False):
+        """The tracking view (xrhip_image_render_view): segments [n][5] = x0, y0, x1, y1, palette index; markers [n][4] = x, y, palette
+        index, r2; palette [n][3] BGR.  -> uint8 [h][w][channels] (a view of rows `stride` bytes apart); with on_device, `out` is a
+        device pointer, `stride` its row pitch, and nothing is returned (KltContext.synchronize completes it)."""
+        sg = np.ascontiguousarray(np.asarray(segments, np.int64).reshape(-1, 5)).astype(np.int32)
+        mk = np.asarray(markers, np.int64).reshape(-1, 4)
+        mk3 = np.empty((len(mk), 3), np.int32)
+        mk3[:, :2] = mk[:, :2]
+        mk3[:, 2] = ((mk[:, 2] & 255) | (mk[:, 3] << 8)).astype(np.uint32).view(np.int32)
+        pal = np.ascontiguousarray(np.asarray(palette, np.uint8).reshape(-1, 3))
+        w, h = self.ctx.w, self.ctx.h
+        if stride is None:
+            stride = w * channels
+        buf = None
+        if on_device:
+            ptr = C.c_void_p(int(out))
+        else:
+            buf = np.full(h * max(int(stride), 1) + 8, 0xA5, np.uint8) if out is None else out
+            ptr = _p(buf)
+        check(L().xrhip_image_render_view(self._h, _p(sg) if len(sg) else None, len(sg), _p(mk3) if len(mk3) else None, len(mk3),
+                                          _p(pal) if len(pal) else None, len(pal), ptr, int(stride), int(channels), 1 if on_device else 0))
+        if on_device:
+            return None
+        return np.lib.stride_tricks.as_strided(buf, shape=(h, w, channels), strides=(int(stride), channels, 1))
 
     def upload_device(self, dev_ptr, stride):
         check(L().xrhip_image_upload_device(self._h, C.c_void_p(int(dev_ptr)), int(stride)))
