@@ -156,6 +156,36 @@ void XRSLAMAmdPushImageDevice(const void *gray_dev, int stride, double timestamp
  * channels 3 or 4 (1: same as XRSLAMAmdPushImageDevice), stride in bytes >= width * channels, any base alignment.  With device
  * undistortion switched on the frame is reduced first and rectified second. */
 void XRSLAMAmdPushImageDeviceColor(const void *pixels_dev, int stride, int channels, double timestamp);
+/* Frames in the layouts cameras, decoders and ROS deliver, from host memory (on_device 0) or HBM, reduced to the 8-bit gray plane the
+ * tracker works on as part of the frame's upload; all integer, per pixel:
+ *   GRAY8           the byte                         BGR8 / BGRA8   as XRSLAM_SENSOR_CAMERA channel 3 / 4
+ *   RGB8 / RGBA8    (R*4899 + G*9617 + B*1868 + 8192) >> 14, byte 3 ignored
+ *   GRAY16          little endian, `bits` significant (8..16, 0 = 16): min(255, v >> (bits - 8)); 16: the high byte
+ *   YUYV / UYVY     packed 4:2:2, the Y byte of each pixel's pair (byte 0 / byte 1)
+ *   NV12 / I420     the luma plane: `stride` is that plane's, and only its `height` rows are read (push a decoder's surface as is)
+ *   P010            the high byte of the luma plane's 16-bit samples; only `height` rows of that plane are read
+ * limited_range (video levels, luma 16..235; not for the four RGB / BGR formats): gray' = min(255, ((max(gray,16) - 16) * 255 + 109) / 219).
+ * Any base alignment, any stride >= width * bytes per pixel.  With device undistortion on: reduced first, rectified second.  A bad
+ * format, bits, stride or flag drops the frame and sets XRSLAMAmdLastError; nothing aborts. */
+typedef enum XRSLAMAmdPixelFormat {
+    XRSLAM_AMD_PIXEL_GRAY8 = 0,
+    XRSLAM_AMD_PIXEL_BGR8,
+    XRSLAM_AMD_PIXEL_BGRA8,
+    XRSLAM_AMD_PIXEL_RGB8,
+    XRSLAM_AMD_PIXEL_RGBA8,
+    XRSLAM_AMD_PIXEL_GRAY16,
+    XRSLAM_AMD_PIXEL_YUYV,
+    XRSLAM_AMD_PIXEL_UYVY,
+    XRSLAM_AMD_PIXEL_NV12,
+    XRSLAM_AMD_PIXEL_I420,
+    XRSLAM_AMD_PIXEL_P010
+} XRSLAMAmdPixelFormat;
+typedef struct XRSLAMAmdFrameFormat {
+    int format;          /* XRSLAMAmdPixelFormat */
+    int bits;            /* GRAY16: significant bits, 8..16; 0 = 16.  Not read for the other formats. */
+    int limited_range;   /* 1: video levels, expanded to 0..255 */
+} XRSLAMAmdFrameFormat;
+void XRSLAMAmdPushImageFormat(const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt, int on_device, double timestamp);
 /* What the reference's dataset readers ask the YamlConfig* for (xrslam-pc/player/src/IO/euroc_dataset_reader.cpp:4-7,16,62-66;
  * tum_dataset_reader.cpp:4-6,67-76): camera_time_offset(), camera_distortion_flag(), camera_distortion(),
  * camera_intrinsic(), camera_resolution().  The `config` out-parameter of XRSLAMCreate is an opaque handle here (the
@@ -286,6 +316,8 @@ void XRSLAMAmdInstanceSetInitialState(XRSLAMAmdInstance *inst, double t, const d
 void XRSLAMAmdInstancePushImageDevice(XRSLAMAmdInstance *inst, const void *gray_dev, int stride, double timestamp);
 void XRSLAMAmdInstancePushImageDeviceColor(XRSLAMAmdInstance *inst, const void *pixels_dev, int stride, int channels,
                                            double timestamp);
+void XRSLAMAmdInstancePushImageFormat(XRSLAMAmdInstance *inst, const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt,
+                                      int on_device, double timestamp);
 void XRSLAMAmdInstanceGetCameraConfig(XRSLAMAmdInstance *inst, XRSLAMAmdCameraConfig *out);
 int XRSLAMAmdInstanceDescribeConfig(XRSLAMAmdInstance *inst, char *buf, int cap);
 void XRSLAMAmdInstanceSetDeviceUndistort(XRSLAMAmdInstance *inst, const char *model);
@@ -331,6 +363,10 @@ int XRSLAMAmdInstanceReplay(XRSLAMAmdInstance *inst, const double *imu7, int n_i
 int XRSLAMAmdInstanceReplayColor(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
                                  const void *frames, size_t frame_bytes, int stride, int channels, int on_device,
                                  int *imu_cursor, int *frame_cursor, int n_steps, double *poses_out8);
+/* The same loop over frames of any XRSLAMAmdFrameFormat; frame_bytes and stride describe the frames as they lie in memory. */
+int XRSLAMAmdInstanceReplayFormat(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
+                                  const void *frames, size_t frame_bytes, int stride, const XRSLAMAmdFrameFormat *fmt, int on_device,
+                                  int *imu_cursor, int *frame_cursor, int n_steps, double *poses_out8);
 
 #ifdef __cplusplus
 }

@@ -95,6 +95,38 @@ int xrhip_image_upload_distorted(xrhip_image *img, const void *gray, int stride_
  * XRHIP_EINVAL for other channel counts, a null pointer, or stride_bytes < width * channels. */
 int xrhip_image_upload_color(xrhip_image *img, const void *pixels, int stride_bytes, int channels, int on_device);
 int xrhip_image_upload_color_distorted(xrhip_image *img, const void *pixels, int stride_bytes, int channels, int on_device);
+/* Camera pixel formats beyond 8-bit gray / BGR / BGRA: what sensors, UVC streams, video decoders and ROS images deliver.  The
+ * frame is reduced to the 8-bit gray plane as part of its upload, all in integers, per pixel:
+ *   GRAY8               1 byte    the byte
+ *   BGR8, BGRA8         3 / 4     (B*1868 + G*9617 + R*4899 + 8192) >> 14, byte 3 ignored (= xrhip_image_upload_color)
+ *   RGB8, RGBA8         3 / 4     the same weights, byte 0 is R
+ *   GRAY16              2 bytes   little endian v = b0 | b1 << 8; `bits` significant (8..16, 0 = 16): min(255, v >> (bits - 8))
+ *   YUYV, UYVY          2 bytes   the Y byte of the pixel's pair: byte 0 / byte 1
+ *   NV12, I420          1 byte    the luma plane; stride_bytes is that plane's, and only its `height` rows are read
+ *   P010                2 bytes   the high byte of the luma plane's 16-bit sample; only `height` rows of that plane are read
+ * `bits` is read for GRAY16 only.  limited_range (video levels, luma 16..235; XRHIP_EINVAL for the four RGB / BGR formats) is applied
+ * to the 8-bit value: min(255, ((max(gray, 16) - 16) * 255 + 109) / 219).
+ * `pixels`: a host pointer, or an HBM pointer when on_device; any base alignment (an odd address for the 2-byte formats included),
+ * any stride_bytes >= width * bytes per pixel.  Of the `height` rows only the first width * bytes-per-pixel bytes are needed: the
+ * device reads whole aligned dwords, each of which holds at least one such byte.  Buffer lifetimes, group behaviour and the
+ * _distorted form (reduced first, rectified second; XRHIP_ESTATE without a map) are those of xrhip_image_upload_color.  GRAY8
+ * without limited_range, BGR8 and BGRA8 forward to the older entry points.  XRHIP_EINVAL (the message names the argument): unknown
+ * `format`, `bits` outside 8..16, `stride` too short, `limited_range` with an RGB / BGR format, a null pointer. */
+#define XRHIP_PIXFMT_GRAY8 0
+#define XRHIP_PIXFMT_BGR8 1
+#define XRHIP_PIXFMT_BGRA8 2
+#define XRHIP_PIXFMT_RGB8 3
+#define XRHIP_PIXFMT_RGBA8 4
+#define XRHIP_PIXFMT_GRAY16 5
+#define XRHIP_PIXFMT_YUYV 6
+#define XRHIP_PIXFMT_UYVY 7
+#define XRHIP_PIXFMT_NV12 8
+#define XRHIP_PIXFMT_I420 9
+#define XRHIP_PIXFMT_P010 10
+int xrhip_image_upload_format(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits, int limited_range,
+                              int on_device);
+int xrhip_image_upload_format_distorted(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits,
+                                        int limited_range, int on_device);
 /* parity aid: the 8-bit frame xrhip_image_preprocess will read */
 int xrhip_debug_get_raw(xrhip_image *img, uint8_t *out);
 /* Development / parity aids of the pyramid build (xrhip_image_preprocess): on = 1 (default) builds the CLAHE plane, the three

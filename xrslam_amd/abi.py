@@ -170,3 +170,8 @@ class MargProblemData(_Factors):
         s.n_landmarks = len(self.inv_depth)
         s.inv_depth = _dpp(self.inv_depth)
         return s
+# XRHIP_PIXFMT_* (include/xrslam_hip.h) = XRSLAMAmdPixelFormat (include/XRSLAM.h)
+PIXFMT_GRAY8, PIXFMT_BGR8, PIXFMT_BGRA8, PIXFMT_RGB8, PIXFMT_RGBA8, PIXFMT_GRAY16, PIXFMT_YUYV, PIXFMT_UYVY, PIXFMT_NV12, \
+    PIXFMT_I420, PIXFMT_P010 = range(11)
+PIXFMT_BYTES = {PIXFMT_GRAY8: 1, PIXFMT_BGR8: 3, PIXFMT_BGRA8: 4, PIXFMT_RGB8: 3, PIXFMT_RGBA8: 4, PIXFMT_GRAY16: 2, PIXFMT_YUYV: 2,
+                PIXFMT_UYVY: 2, PIXFMT_NV12: 1, PIXFMT_I420: 1, PIXFMT_P010: 2}   # bytes per pixel read (NV12 / I420 / P010: the luma plane's)

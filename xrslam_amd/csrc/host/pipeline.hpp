@@ -19,6 +19,7 @@
 // re-integrations, image preprocessing): DESIGN.md section 4.5.
 #pragma once
 #include <chrono>
+#include <climits>
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -41,6 +42,7 @@
 #include "config.hpp"
 #include "map.hpp"
 #include "parsac.hpp"
+#include "pixel_format.hpp"
 #include "two_view.hpp"
 #include "undistort_map.hpp"
 
@@ -50,12 +52,16 @@
 extern "C" {
 int xrhip_image_upload_color(xrhip_image *img, const void *pixels, int stride_bytes, int channels, int on_device) __attribute__((weak));
 int xrhip_image_upload_color_distorted(xrhip_image *img, const void *pixels, int stride_bytes, int channels, int on_device) __attribute__((weak));
+// (likewise the uploads of the other pixel formats: Pipeline::make_image reduces such frames with pixel_format.hpp's formulas)
+int xrhip_image_upload_format(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits, int limited_range, int on_device) __attribute__((weak));
+int xrhip_image_upload_format_distorted(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits, int limited_range, int on_device) __attribute__((weak));
 // (likewise the tracking view's renderer: the feature snapshot below needs nothing of it)
 int xrhip_image_render_view(xrhip_image *img, const xrhip_view_segment *segs, int n_segs, const xrhip_view_marker *markers, int n_markers,
                             const uint8_t *palette_bgr, int n_palette, void *out, int stride_bytes, int channels, int on_device) __attribute__((weak));
 }
 
 namespace xrh {
+inline bool have_format_upload() { return xrhip_image_upload_format != nullptr && xrhip_image_upload_format_distorted != nullptr; }
 inline bool have_color_upload() { return xrhip_image_upload_color != nullptr && xrhip_image_upload_color_distorted != nullptr; }
 
 struct HipError : std::runtime_error {
@@ -304,30 +310,48 @@ struct Pipeline {
     // channels 1: 8-bit gray; 3 / 4: interleaved BGR / BGRA, reduced to gray by the frame's upload (xrhip_image_upload_color) -- or
     // here, where the library behind xrslam_hip.h has no colour upload (the CPU reference build: its host arithmetic is what the
     // device's is compared against)
+    // format other than NO_PIXEL_FORMAT (XRHIP_PIXFMT_*, with its bits / limited_range) takes the place of channels: GRAY8 without a range flag, BGR8 and
+    // BGRA8 are the frames above; every other format is reduced by xrhip_image_upload_format -- or here, with the same integer formulas
+    // (pixel_format.hpp), where the library has no such upload.
+    static constexpr int NO_PIXEL_FORMAT = INT_MIN;
     std::vector<uint8_t> gray_scratch;
-    std::shared_ptr<HipImage> make_image(const uint8_t *gray, int stride, double t, bool device_ptr, int channels = 1) {
-        if (channels != 1 && channels != 3 && channels != 4) throw std::runtime_error("Image channel is not supported!");
+    std::shared_ptr<HipImage> make_image(const uint8_t *gray, int stride, double t, bool device_ptr, int channels = 1, int format = NO_PIXEL_FORMAT,
+                                         int bits = 0, int limited_range = 0) {
+        const int cols = (int)config.cam_resolution[0], rows = (int)config.cam_resolution[1];
+        PixelFormat pf;
+        bool by_format = false;
+        if (format != NO_PIXEL_FORMAT) {
+            if (const char *why = describe_pixel_format(format, bits, limited_range, pf))
+                throw std::runtime_error(std::string("Image format is not supported: ") + why);
+            if (!gray || (long long)stride < (long long)cols * pf.bpp)
+                throw std::runtime_error("Image format is not supported: null pixels or stride < width * bytes per pixel");
+            by_format = pf.bpp == 2 || pf.rgb || pf.limited;
+            channels = pf.bpp;
+        }
+        if (channels != 1 && channels != 3 && channels != 4 && !by_format) throw std::runtime_error("Image channel is not supported!");
         auto img = std::make_shared<HipImage>();
         img->owner = this;
         img->h = acquire_image();
         img->t = t;
-        img->w = (int)config.cam_resolution[0];
-        img->hgt = (int)config.cam_resolution[1];
-        if (channels != 1 && !have_color_upload()) {   // cv::cvtColor BGR(A)2GRAY: (B*1868 + G*9617 + R*4899 + 8192) >> 14
-            const int cols = img->w, rows = img->hgt;
+        img->w = cols;
+        img->hgt = rows;
+        if (by_format ? !have_format_upload() : channels != 1 && !have_color_upload()) {
+            // BGR(A): cv::cvtColor BGR(A)2GRAY, (B*1868 + G*9617 + R*4899 + 8192) >> 14
+            if (!by_format) pf.bpp = channels;
             gray_scratch.resize((size_t)cols * rows);
-            for (int y = 0; y < rows; ++y)
-                for (int x = 0; x < cols; ++x) {
-                    const uint8_t *px = gray + (size_t)y * stride + (size_t)x * channels;
-                    gray_scratch[(size_t)y * cols + x] = (uint8_t)((px[0] * 1868 + px[1] * 9617 + px[2] * 4899 + 8192) >> 14);
-                }
+            reduce_frame(gray_scratch.data(), gray, stride, cols, rows, pf);
             gray = gray_scratch.data();
             stride = cols;
             channels = 1;
+            by_format = false;
         }
         // a member of an instance group starts its frame together with the other members (timing only: xrslam_hip.h, frame gate)
         if (group) xrhip_klt_frame_gate(klt);
-        if (channels != 1) {
+        if (by_format) {
+            if (undistort_on_device)
+                hip_check(xrhip_image_upload_format_distorted(img->h, gray, stride, format, bits, limited_range, device_ptr ? 1 : 0), "xrhip_image_upload_format_distorted");
+            else hip_check(xrhip_image_upload_format(img->h, gray, stride, format, bits, limited_range, device_ptr ? 1 : 0), "xrhip_image_upload_format");
+        } else if (channels != 1) {
             if (undistort_on_device)
                 hip_check(xrhip_image_upload_color_distorted(img->h, gray, stride, channels, device_ptr ? 1 : 0), "xrhip_image_upload_color_distorted");
             else hip_check(xrhip_image_upload_color(img->h, gray, stride, channels, device_ptr ? 1 : 0), "xrhip_image_upload_color");

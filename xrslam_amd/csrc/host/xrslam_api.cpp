@@ -248,6 +248,24 @@ void impl_push_image_device(Manager &m, const void *gray_dev, int stride, double
     });
 }
 
+// A frame in one of the XRSLAMAmdPixelFormat layouts, from host memory or HBM.  A bad format drops the frame and sets the last error.
+void impl_push_image_format(Manager &m, const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt, int on_device, double timestamp) {
+    if (!m.sys) return;
+    bind_device(m);
+    guarded(m, [&] {
+        try {
+            std::lock_guard<std::mutex> lk(m.input_mutex);
+            if (!fmt || !pixels) throw std::runtime_error("Image format is not supported: null pixels or format");
+            m.cur_image = m.sys->P.make_image(static_cast<const uint8_t *>(pixels), stride, timestamp, on_device != 0, 1, fmt->format, fmt->bits,
+                                              fmt->limited_range);
+        } catch (...) {
+            std::lock_guard<std::mutex> lk(m.input_mutex);
+            m.cur_image.reset();
+            throw;
+        }
+    });
+}
+
 void impl_get_camera_config(Manager &m, XRSLAMAmdCameraConfig *out) {
     if (!out) return;
     std::memset(out, 0, sizeof(*out));
@@ -456,6 +474,9 @@ void XRSLAMAmdPushImageDevice(const void *gray_dev, int stride, double timestamp
 void XRSLAMAmdPushImageDeviceColor(const void *pixels_dev, int stride, int channels, double timestamp) {
     impl_push_image_device(mgr(), pixels_dev, stride, timestamp, channels);
 }
+void XRSLAMAmdPushImageFormat(const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt, int on_device, double timestamp) {
+    impl_push_image_format(mgr(), pixels, stride, fmt, on_device, timestamp);
+}
 void XRSLAMAmdGetCameraConfig(XRSLAMAmdCameraConfig *out) { impl_get_camera_config(mgr(), out); }
 int XRSLAMAmdDescribeConfig(char *buf, int cap) { return impl_describe_config(mgr(), buf, cap); }
 void XRSLAMAmdSetDeviceUndistort(const char *model) { impl_set_device_undistort(mgr(), model); }
@@ -513,6 +534,10 @@ void XRSLAMAmdInstancePushImageDevice(XRSLAMAmdInstance *inst, const void *gray_
 void XRSLAMAmdInstancePushImageDeviceColor(XRSLAMAmdInstance *inst, const void *pixels_dev, int stride, int channels,
                                            double timestamp) {
     if (inst) impl_push_image_device(inst->m, pixels_dev, stride, timestamp, channels);
+}
+void XRSLAMAmdInstancePushImageFormat(XRSLAMAmdInstance *inst, const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt,
+                                      int on_device, double timestamp) {
+    if (inst) impl_push_image_format(inst->m, pixels, stride, fmt, on_device, timestamp);
 }
 void XRSLAMAmdInstanceGetCameraConfig(XRSLAMAmdInstance *inst, XRSLAMAmdCameraConfig *out) {
     if (inst) impl_get_camera_config(inst->m, out);
@@ -603,9 +628,10 @@ void XRSLAMAmdGroupGetStats(XRSLAMAmdGroup *grp, void *out, int reset) {
 // The player's loop (xrslam-pc/player/src/main.cpp:116-169) for n_steps camera frames of a pre-staged sequence, without a
 // host-language round trip per sensor sample: at equal timestamps gyroscope, then accelerometer, then camera
 // (IO/async_dataset_reader.cpp:41-48); RunOneFrame and the state / pose query after every image.
-int XRSLAMAmdInstanceReplayColor(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
-                                 const void *frames, size_t frame_bytes, int stride, int channels, int on_device,
-                                 int *imu_cursor, int *frame_cursor, int n_steps, double *poses_out8) {
+// (fmt: the frames' XRSLAMAmdFrameFormat, or null for `channels`)
+static int replay(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames, const void *frames,
+                  size_t frame_bytes, int stride, int channels, const XRSLAMAmdFrameFormat *fmt, int on_device, int *imu_cursor,
+                  int *frame_cursor, int n_steps, double *poses_out8) {
     if (!inst || !imu7 || !cam_t || !frames || !imu_cursor || !frame_cursor) return -1;
     Manager &m = inst->m;
     int n_poses = 0;
@@ -632,7 +658,9 @@ int XRSLAMAmdInstanceReplayColor(XRSLAMAmdInstance *inst, const double *imu7, in
         }
         *imu_cursor = k;
         const unsigned char *img = static_cast<const unsigned char *>(frames) + (size_t)fk * frame_bytes;
-        if (on_device) {
+        if (fmt) {
+            impl_push_image_format(m, img, stride, fmt, on_device, t);
+        } else if (on_device) {
             impl_push_image_device(m, img, stride, t, channels);
         } else {
             XRSLAMImage im;
@@ -658,6 +686,21 @@ int XRSLAMAmdInstanceReplayColor(XRSLAMAmdInstance *inst, const double *imu7, in
         *frame_cursor = fk + 1;
     }
     return n_poses;
+}
+
+int XRSLAMAmdInstanceReplayColor(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
+                                 const void *frames, size_t frame_bytes, int stride, int channels, int on_device,
+                                 int *imu_cursor, int *frame_cursor, int n_steps, double *poses_out8) {
+    return replay(inst, imu7, n_imu, cam_t, n_frames, frames, frame_bytes, stride, channels, nullptr, on_device, imu_cursor, frame_cursor,
+                  n_steps, poses_out8);
+}
+
+int XRSLAMAmdInstanceReplayFormat(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
+                                  const void *frames, size_t frame_bytes, int stride, const XRSLAMAmdFrameFormat *fmt, int on_device,
+                                  int *imu_cursor, int *frame_cursor, int n_steps, double *poses_out8) {
+    if (!fmt) return -1;
+    return replay(inst, imu7, n_imu, cam_t, n_frames, frames, frame_bytes, stride, 1, fmt, on_device, imu_cursor, frame_cursor, n_steps,
+                  poses_out8);
 }
 
 int XRSLAMAmdInstanceReplay(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,

@@ -4,6 +4,7 @@
 #include "../../include/xrslam_hip.h"
 #include "common.hip.h"
 #include "group.hip.h"
+#include "host/pixel_format.hpp"
 #include "host_select.hpp"
 #include "klt_kernels.hip.h"
 
@@ -663,8 +664,9 @@ static int ensure_slot_bytes(xrhip_klt *c, size_t bytes) {
 
 // Copies a host frame into the next pinned slot and queues its transfer into `dst` (w*h, dense); the caller's buffer is free on return.
 // bpp 1: a gray frame, DMA (or the group's upload launch).  bpp 3 / 4: a BGR / BGRA frame, reduced to gray by k_upload, which reads
-// the mapped slot -- the plane in HBM is written once and the colour bytes cross the host link once.
-static int stage_host_frame(xrhip_klt *c, const uint8_t *pixels, int stride, uint8_t *dst, int bpp = 1) {
+// the mapped slot -- the plane in HBM is written once and the colour bytes cross the host link once.  The same for the other
+// pixel formats (fmt: UPF_*, klt_kernels.hip.h), rows of w * bpp bytes; a 1-byte format with fmt set goes through k_upload too.
+static int stage_host_frame(xrhip_klt *c, const uint8_t *pixels, int stride, uint8_t *dst, int bpp = 1, int fmt = 0) {
     const size_t row = (size_t)c->w * bpp;
     if (bpp != 1) {
         const int rc = ensure_slot_bytes(c, row * c->h);
@@ -684,13 +686,12 @@ static int stage_host_frame(xrhip_klt *c, const uint8_t *pixels, int stride, uin
         if (rc) return rc;
         uint8_t *buf = c->up_buf[slot];
         if ((size_t)stride == row) copy_to_pinned(buf, pixels, row * c->h);
-        else
-            for (int y = 0; y < c->h; ++y) std::memcpy(buf + (size_t)y * row, pixels + (size_t)y * stride, row);
+        else xrh::pack_rows(buf, pixels, stride, row, c->h);
         uint8_t *dbuf = nullptr;
         XR_HIP(hipHostGetDevicePointer((void **)&dbuf, buf, 0));
         rc = flush_upload(c);   // (an earlier frame nobody preprocessed)
         if (rc) return rc;
-        c->a_upload = UploadArgs{dbuf, (int)row, dst, c->w, c->h, bpp};
+        c->a_upload = UploadArgs{dbuf, (int)row, dst, c->w, c->h, bpp, fmt};
         c->uploads_unsynced++;
         c->upload_pending = true;   // submitted with the frame's preprocessing (xrhip_image_preprocess), or by whoever reads the plane first
         return XRHIP_OK;
@@ -700,14 +701,14 @@ static int stage_host_frame(xrhip_klt *c, const uint8_t *pixels, int stride, uin
     if ((size_t)stride == row) {
         copy_to_pinned(buf, pixels, row * c->h);
     } else {
-        for (int y = 0; y < c->h; ++y) std::memcpy(buf + (size_t)y * row, pixels + (size_t)y * stride, row);
+        xrh::pack_rows(buf, pixels, stride, row, c->h);
     }
-    if (bpp == 1) {
+    if (bpp == 1 && fmt == 0) {
         XR_HIP(hipMemcpyAsync(dst, buf, (size_t)c->w * c->h, hipMemcpyHostToDevice, c->stream));
     } else {
         uint8_t *dbuf = nullptr;
         XR_HIP(hipHostGetDevicePointer((void **)&dbuf, buf, 0));
-        c->a_upload = UploadArgs{dbuf, (int)row, dst, c->w, c->h, bpp};
+        c->a_upload = UploadArgs{dbuf, (int)row, dst, c->w, c->h, bpp, fmt};
         const int rc = klt_issue(c, c->rq_upload, GK_UPLOAD, &c->a_upload, launch_upload_batch);
         if (rc) return rc;
     }
@@ -831,16 +832,17 @@ int xrhip_image_upload_device(xrhip_image *im, const void *gray_dev, int stride)
     return XRHIP_OK;
 }
 
-// A BGR / BGRA frame into `dst` as gray: from a host buffer through the pinned slots, or from HBM where it lies
-static int upload_color_into(xrhip_klt *c, const void *pixels, int stride, int channels, int on_device, uint8_t *dst) {
-    if (!on_device) return stage_host_frame(c, static_cast<const uint8_t *>(pixels), stride, dst, channels);
+// A BGR / BGRA frame (or, with fmt, a frame of another pixel format of `channels` bytes per pixel) into `dst` as gray: from a host
+// buffer through the pinned slots, or from HBM where it lies
+static int upload_color_into(xrhip_klt *c, const void *pixels, int stride, int channels, int on_device, uint8_t *dst, int fmt = 0) {
+    if (!on_device) return stage_host_frame(c, static_cast<const uint8_t *>(pixels), stride, dst, channels, fmt);
     if (c->group) {
         int rc = group_wait_launched(&c->rq_upload);
         if (rc) return rc;
         rc = flush_upload(c);
         if (rc) return rc;
     }
-    c->a_upload = UploadArgs{static_cast<const uint8_t *>(pixels), stride, dst, c->w, c->h, channels};
+    c->a_upload = UploadArgs{static_cast<const uint8_t *>(pixels), stride, dst, c->w, c->h, channels, fmt};
     if (c->group) {
         c->upload_pending = true;   // with the frame's preprocessing, like xrhip_image_upload_device
         return XRHIP_OK;
@@ -876,6 +878,47 @@ int xrhip_image_upload_color_distorted(xrhip_image *im, const void *pixels, int 
     if (!c->have_undist) return xr_fail(XRHIP_ESTATE, "xrhip_image_upload_color_distorted: no undistortion map (xrhip_klt_set_undistort_map)");
     // gray first, rectified second: the reduced frame takes the place of the frame a gray camera would have recorded
     rc = upload_color_into(c, pixels, stride, channels, on_device, c->undist_src);
+    if (rc) return rc;
+    return xrhip_image_upload_distorted(im, c->undist_src, c->w, 1);
+}
+
+// The pixel formats (xrslam_hip.h: XRHIP_PIXFMT_*): GRAY8 without a range flag, BGR8 and BGRA8 are the older entry points' frames;
+// every other one is a k_upload request of its bytes per pixel and UPF_* word
+static int check_format_args(const char *who, const xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited,
+                             xrh::PixelFormat &pf) {
+    if (!im || !pixels) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": null argument").c_str());
+    if (const char *why = xrh::describe_pixel_format(format, bits, limited, pf)) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": " + why).c_str());
+    if ((long long)stride < (long long)im->ctx->w * pf.bpp) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": stride_bytes < width * bytes per pixel").c_str());
+    return XRHIP_OK;
+}
+static int upf_word(const xrh::PixelFormat &pf) {
+    return (pf.bpp == 2 ? (int)pf.shift | (pf.mask == 0xffu ? UPF_LOW_BYTE : 0) : 0) | (pf.rgb ? UPF_RGB : 0) | (pf.limited ? UPF_LIMITED : 0);
+}
+
+int xrhip_image_upload_format(xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited, int on_device) {
+    xrh::PixelFormat pf;
+    int rc = check_format_args("xrhip_image_upload_format", im, pixels, stride, format, bits, limited, pf);
+    if (rc) return rc;
+    const int fmt = upf_word(pf);
+    if (fmt == 0 && pf.bpp != 2) return xrhip_image_upload_color(im, pixels, stride, pf.bpp, on_device);   // gray, BGR, BGRA
+    rc = upload_color_into(im->ctx, pixels, stride, pf.bpp, on_device, im->raw, fmt);
+    if (rc) return rc;
+    im->have_raw = true;
+    im->have_pyramid = false;
+    im->want_detect = false;
+    im->detect_seq = 0;
+    return XRHIP_OK;
+}
+
+int xrhip_image_upload_format_distorted(xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited, int on_device) {
+    xrh::PixelFormat pf;
+    int rc = check_format_args("xrhip_image_upload_format_distorted", im, pixels, stride, format, bits, limited, pf);
+    if (rc) return rc;
+    const int fmt = upf_word(pf);
+    if (fmt == 0 && pf.bpp != 2) return xrhip_image_upload_color_distorted(im, pixels, stride, pf.bpp, on_device);
+    xrhip_klt *c = im->ctx;
+    if (!c->have_undist) return xr_fail(XRHIP_ESTATE, "xrhip_image_upload_format_distorted: no undistortion map (xrhip_klt_set_undistort_map)");
+    rc = upload_color_into(c, pixels, stride, pf.bpp, on_device, c->undist_src, fmt);   // reduced first, rectified second
     if (rc) return rc;
     return xrhip_image_upload_distorted(im, c->undist_src, c->w, 1);
 }

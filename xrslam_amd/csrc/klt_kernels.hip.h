@@ -1422,48 +1422,81 @@ struct UploadArgs {
     int sstride;
     uint8_t *dst;   // dense w x h
     int w, h;
-    int bpp;        // bytes per source pixel: 0 / 1 gray (a copy), 3 BGR, 4 BGRA (reduced to gray on the way)
+    int bpp;        // bytes per source pixel: 0 / 1 gray (a copy), 2 a 16-bit sample or a Y byte with its chroma, 3 / 4 BGR(A) / RGB(A)
+    int fmt;        // UPF_* below; 0: what bpp alone meant before there were formats (gray copy, BGR, BGRA)
 };
-// cv::cvtColor BGR(A)2GRAY in its 14-bit fixed point (the host pipeline's and the player's arithmetic); at most 255
-__device__ __forceinline__ uint32_t bgr_to_gray(uint32_t b, uint32_t g, uint32_t r) {
-    return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14;
+// UploadArgs::fmt.  bpp 2: gray = min(255, (v & mask) >> shift) of the little-endian sample v -- GRAY16 with `bits` significant:
+// shift = bits - 8; P010 and UYVY: shift 8; YUYV: the low byte.  bpp 1 / 2: UPF_LIMITED expands video levels (16..235) to 0..255.
+constexpr int UPF_SHIFT = 15;      // bits 0-3: right shift of a 2-byte sample, 0..8
+constexpr int UPF_LOW_BYTE = 16;   // 2-byte sample: its low byte alone
+constexpr int UPF_RGB = 32;        // 3 / 4 bytes: byte 0 is R, not B
+constexpr int UPF_LIMITED = 64;    // 1 / 2 bytes: gray' = min(255, ((max(gray, 16) - 16) * 255 + 109) / 219)
+// cv::cvtColor BGR(A)2GRAY / RGB(A)2GRAY in its 14-bit fixed point (the host pipeline's and the player's arithmetic); at most 255.
+// w0 / w2: the weights of bytes 0 and 2 (1868 / 4899 for BGR, swapped for RGB).
+__device__ __forceinline__ uint32_t bgr_to_gray(uint32_t c0, uint32_t g, uint32_t c2, uint32_t w0, uint32_t w2) {
+    return (c0 * w0 + g * 9617u + c2 * w2 + 8192u) >> 14;
 }
-// A colour frame (any base alignment, any stride >= w * BPP) reduced into the dense gray plane.  A lane owns four consecutive pixels of
-// the plane = one dword store.  Where the four lie in one row it fetches the aligned dwords that cover their 12 / 16 source bytes --
-// neighbouring lanes read neighbouring dwords, and every fetched dword holds at least one byte of the frame, so nothing outside the
-// pages of the frame is touched -- and shifts them into place; four pixels that straddle a row end (w % 4 != 0) and the plane's last
-// w * h % 4 pixels go byte by byte.
-template <int BPP> __device__ __forceinline__ void d_upload_color(const UploadArgs &a) {
+// A 1 / 2-byte pixel's value (mask, shift: see UPF_*) to gray
+__device__ __forceinline__ uint32_t narrow_to_gray(uint32_t v, uint32_t mask, uint32_t shift, bool limited) {
+    uint32_t g = min(255u, (v & mask) >> shift);
+    if (limited) g = min(255u, ((max(g, 16u) - 16u) * 255u + 109u) / 219u);
+    return g;
+}
+// The ND dwords that start at byte address `ad` (any alignment) from the aligned dwords that cover them: ND loads, one more where
+// ad is not a multiple of 4 -- and then that dword holds the last of the 4 * ND bytes, so every fetched dword holds one of them.
+template <int ND> __device__ __forceinline__ void load_dwords_unaligned(uintptr_t ad, uint32_t (&d)[ND + 1]) {
+    const uint32_t *q = reinterpret_cast<const uint32_t *>(ad & ~(uintptr_t)3);
+    const uint32_t sh = (uint32_t)(ad & 3) * 8u;
+#pragma unroll
+    for (int k = 0; k < ND; ++k) d[k] = q[k];
+    d[ND] = 0;
+    if (sh) {
+        d[ND] = q[ND];
+#pragma unroll
+        for (int k = 0; k < ND; ++k) d[k] = (d[k] >> sh) | (d[k + 1] << (32u - sh));
+    }
+}
+// A frame of BPP bytes per pixel (any base alignment, any stride >= w * BPP) reduced into the dense gray plane.  A lane owns four
+// consecutive pixels of the plane = one dword store.  Where the four lie in one row it fetches the aligned dwords that cover their
+// 4 * BPP source bytes -- neighbouring lanes read neighbouring dwords (BPP 2: a wavefront's loads cover 512 contiguous bytes), and
+// every fetched dword holds at least one byte of the frame, so nothing outside the pages of the frame is touched -- and shifts them
+// into place; four pixels that straddle a row end (w % 4 != 0) and the plane's last w * h % 4 pixels go byte by byte.
+// BPP 3 / 4: BGR(A) or RGB(A).  BPP 2: a 16-bit sample (misaligned at an odd base: the shift puts it together) or Y + chroma.
+// BPP 1: a gray / luma byte that is not simply copied (limited range).
+template <int BPP> __device__ __forceinline__ void d_upload_reduce(const UploadArgs &a) {
     const uint32_t w = (uint32_t)a.w, total = w * (uint32_t)a.h;
     const uint32_t n4 = (total + 3u) >> 2;
     constexpr int ND = BPP;   // dwords of four pixels
+    const bool rgb = (a.fmt & UPF_RGB) != 0, limited = (a.fmt & UPF_LIMITED) != 0;
+    const uint32_t w0 = rgb ? 4899u : 1868u, w2 = rgb ? 1868u : 4899u;
+    const uint32_t mask = (BPP == 1 || (a.fmt & UPF_LOW_BYTE)) ? 0xffu : 0xffffu, shift = BPP == 2 ? (uint32_t)(a.fmt & UPF_SHIFT) : 0u;
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n4; i += gridDim.x * 256u) {
         const uint32_t p0 = i << 2;
         const uint32_t y = p0 / w, x = p0 - y * w;
         if (x + 4u <= w) {   // (p0 + 4 <= total follows)
-            const uintptr_t ad = reinterpret_cast<uintptr_t>(a.src + (size_t)y * (size_t)a.sstride + (size_t)x * BPP);
-            const uint32_t *q = reinterpret_cast<const uint32_t *>(ad & ~(uintptr_t)3);
-            const uint32_t sh = (uint32_t)(ad & 3) * 8u;
             uint32_t d[ND + 1];
-#pragma unroll
-            for (int k = 0; k < ND; ++k) d[k] = q[k];
-            d[ND] = 0;
-            if (sh) {
-                d[ND] = q[ND];
-#pragma unroll
-                for (int k = 0; k < ND; ++k) d[k] = (d[k] >> sh) | (d[k + 1] << (32u - sh));
-            }
+            load_dwords_unaligned<ND>(reinterpret_cast<uintptr_t>(a.src + (size_t)y * (size_t)a.sstride + (size_t)x * BPP), d);
             uint32_t g0, g1, g2, g3;
             if (BPP == 4) {
-                g0 = bgr_to_gray(d[0] & 255u, (d[0] >> 8) & 255u, (d[0] >> 16) & 255u);
-                g1 = bgr_to_gray(d[1] & 255u, (d[1] >> 8) & 255u, (d[1] >> 16) & 255u);
-                g2 = bgr_to_gray(d[2] & 255u, (d[2] >> 8) & 255u, (d[2] >> 16) & 255u);
-                g3 = bgr_to_gray(d[ND - 1] & 255u, (d[ND - 1] >> 8) & 255u, (d[ND - 1] >> 16) & 255u);
+                g0 = bgr_to_gray(d[0] & 255u, (d[0] >> 8) & 255u, (d[0] >> 16) & 255u, w0, w2);
+                g1 = bgr_to_gray(d[1] & 255u, (d[1] >> 8) & 255u, (d[1] >> 16) & 255u, w0, w2);
+                g2 = bgr_to_gray(d[2] & 255u, (d[2] >> 8) & 255u, (d[2] >> 16) & 255u, w0, w2);
+                g3 = bgr_to_gray(d[ND - 1] & 255u, (d[ND - 1] >> 8) & 255u, (d[ND - 1] >> 16) & 255u, w0, w2);
+            } else if (BPP == 3) {
+                g0 = bgr_to_gray(d[0] & 255u, (d[0] >> 8) & 255u, (d[0] >> 16) & 255u, w0, w2);
+                g1 = bgr_to_gray(d[0] >> 24, d[1] & 255u, (d[1] >> 8) & 255u, w0, w2);
+                g2 = bgr_to_gray((d[1] >> 16) & 255u, d[1] >> 24, d[2] & 255u, w0, w2);
+                g3 = bgr_to_gray((d[2] >> 8) & 255u, (d[2] >> 16) & 255u, d[2] >> 24, w0, w2);
+            } else if (BPP == 2) {
+                g0 = narrow_to_gray(d[0], mask, shift, limited);
+                g1 = narrow_to_gray(d[0] >> 16, mask, shift, limited);
+                g2 = narrow_to_gray(d[ND - 1], mask, shift, limited);
+                g3 = narrow_to_gray(d[ND - 1] >> 16, mask, shift, limited);
             } else {
-                g0 = bgr_to_gray(d[0] & 255u, (d[0] >> 8) & 255u, (d[0] >> 16) & 255u);
-                g1 = bgr_to_gray(d[0] >> 24, d[1] & 255u, (d[1] >> 8) & 255u);
-                g2 = bgr_to_gray((d[1] >> 16) & 255u, d[1] >> 24, d[2] & 255u);
-                g3 = bgr_to_gray((d[2] >> 8) & 255u, (d[2] >> 16) & 255u, d[2] >> 24);
+                g0 = narrow_to_gray(d[0], mask, 0u, limited);
+                g1 = narrow_to_gray(d[0] >> 8, mask, 0u, limited);
+                g2 = narrow_to_gray(d[0] >> 16, mask, 0u, limited);
+                g3 = narrow_to_gray(d[0] >> 24, mask, 0u, limited);
             }
             reinterpret_cast<uint32_t *>(a.dst)[i] = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
         } else {
@@ -1471,7 +1504,8 @@ template <int BPP> __device__ __forceinline__ void d_upload_color(const UploadAr
             for (uint32_t p = p0; p < pe; ++p) {
                 const uint32_t py = p / w, px = p - py * w;
                 const uint8_t *s = a.src + (size_t)py * (size_t)a.sstride + (size_t)px * BPP;
-                a.dst[p] = (uint8_t)bgr_to_gray(s[0], s[1], s[2]);
+                if (BPP >= 3) a.dst[p] = (uint8_t)bgr_to_gray(s[0], s[1], s[2], w0, w2);
+                else a.dst[p] = (uint8_t)narrow_to_gray(BPP == 2 ? (uint32_t)s[0] | ((uint32_t)s[BPP - 1] << 8) : (uint32_t)s[0], mask, shift, limited);
             }
         }
     }
@@ -1479,8 +1513,10 @@ template <int BPP> __device__ __forceinline__ void d_upload_color(const UploadAr
 __global__ __launch_bounds__(256) void k_upload(Batch<UploadArgs> b) {
     const UploadArgs &a = b.e[blockIdx.z];
     if (!a.src) return;
-    if (a.bpp == 3) return d_upload_color<3>(a);
-    if (a.bpp == 4) return d_upload_color<4>(a);
+    if (a.bpp == 3) return d_upload_reduce<3>(a);
+    if (a.bpp == 4) return d_upload_reduce<4>(a);
+    if (a.bpp == 2) return d_upload_reduce<2>(a);
+    if (a.fmt & UPF_LIMITED) return d_upload_reduce<1>(a);
     const size_t total = (size_t)a.w * a.h;
     if (a.sstride == a.w && (total & 15) == 0 && ((reinterpret_cast<uintptr_t>(a.src) | reinterpret_cast<uintptr_t>(a.dst)) & 15) == 0) {
         const uint4 *s4 = reinterpret_cast<const uint4 *>(a.src);

@@ -166,16 +166,21 @@ inline std::vector<Event> merge_events(const std::vector<CameraRow> &cam, const 
 // ------------------------------------------------------------------------------------------------ PNG
 struct GrayImage {
     int w = 0, h = 0;
-    int channels = 1;          // 1 gray; 3 / 4: interleaved BGR / BGRA (decode_png with keep_color)
+    int channels = 1;          // bytes per pixel.  1 gray; 3 / 4: interleaved BGR / BGRA (decode_png with PNG_KEEP_BGR) ...
+    int pixel_format = -1;     // ... unless this is an XRSLAMAmdPixelFormat: 3 / 4 RGB8 / RGBA8 (PNG_KEEP_RGB*), 5 GRAY16 (PNG_KEEP_GRAY16)
     std::vector<uint8_t> px;   // row-major, stride w * channels
 };
+// what decode_png hands out instead of 8-bit gray, where the file has it
+enum { PNG_GRAY = 0, PNG_KEEP_BGR = 1, PNG_KEEP_RGB = 2, PNG_KEEP_RGBA = 3, PNG_KEEP_GRAY16 = 4 };
 
 inline uint32_t be32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 
 // 8-bit, non-interlaced, colour types 0 (grey), 2 (RGB), 4 (grey+alpha), 6 (RGBA).  Colour is reduced with the
 // integer weights of cv::cvtColor(BGR2GRAY): (R*4899 + G*9617 + B*1868 + 8192) >> 14 -- or, with keep_color, handed out as
 // the BGR / BGRA pixels cv::imread(IMREAD_UNCHANGED) would give, for a caller that pushes them with channel 3 / 4.
-inline GrayImage decode_png(const std::vector<uint8_t> &file, bool keep_color = false) {
+// keep = PNG_KEEP_RGB / PNG_KEEP_RGBA: a colour file as 3 / 4 bytes per pixel in the file's own order (alpha dropped / 255 where the
+// file and the request differ); PNG_KEEP_GRAY16: a 16-bit gray file as little-endian 16-bit samples.  Other files: as without.
+inline GrayImage decode_png(const std::vector<uint8_t> &file, int keep = PNG_GRAY) {
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
     if (file.size() < 8 || std::memcmp(file.data(), sig, 8) != 0) throw std::runtime_error("png: bad signature");
     size_t pos = 8;
@@ -222,8 +227,18 @@ inline GrayImage decode_png(const std::vector<uint8_t> &file, bool keep_color = 
     GrayImage img;
     img.w = w;
     img.h = h;
-    const bool color = keep_color && ch >= 3;
+    const bool color = keep == PNG_KEEP_BGR && ch >= 3;
+    const bool rgb = (keep == PNG_KEEP_RGB || keep == PNG_KEEP_RGBA) && ch >= 3;
+    const bool gray16 = keep == PNG_KEEP_GRAY16 && ch <= 2 && depth == 16;
     if (color) img.channels = ch;
+    if (rgb) {
+        img.channels = keep == PNG_KEEP_RGB ? 3 : 4;
+        img.pixel_format = keep == PNG_KEEP_RGB ? 3 : 4;
+    }
+    if (gray16) {
+        img.channels = 2;
+        img.pixel_format = 5;
+    }
     img.px.resize((size_t)w * h * img.channels);
     for (int y = 0; y < h; ++y) {
         const uint8_t *line = &raw[(stride + 1) * (size_t)y];
@@ -251,6 +266,15 @@ inline GrayImage decode_png(const std::vector<uint8_t> &file, bool keep_color = 
                 d[1] = px[bps];
                 d[2] = px[0];
                 if (ch == 4) d[3] = px[3 * bps];
+            } else if (rgb) {
+                uint8_t *d = dst + (size_t)x * img.channels;
+                d[0] = px[0];
+                d[1] = px[bps];
+                d[2] = px[2 * bps];
+                if (img.channels == 4) d[3] = ch == 4 ? px[3 * bps] : 255;
+            } else if (gray16) {   // big endian in the file
+                dst[2 * (size_t)x] = px[1];
+                dst[2 * (size_t)x + 1] = px[0];
             } else if (ch <= 2) dst[x] = px[0];
             else dst[x] = (uint8_t)((px[0] * 4899 + px[bps] * 9617 + px[2 * bps] * 1868 + 8192) >> 14);
         }

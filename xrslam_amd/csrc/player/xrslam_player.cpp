@@ -7,9 +7,11 @@
 //
 //   xrslam-player --slam configs/euroc_slam.yaml --device configs/euroc_sensor.yaml --euroc <dir>/mav0
 //                 [--out traj.tum] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined]
-//                 [--push-color]
+//                 [--push-color] [--push-format gray16|rgb|rgba]
 //
 // (--push-color: a colour PNG is pushed as BGR / BGRA with channel 3 / 4 and reduced to gray by the library instead of by the reader.)
+// (--push-format: a 16-bit PNG is handed to the library as GRAY16 instead of being stripped to its high byte by the reader; a colour
+// PNG as RGB8 / RGBA8 -- XRSLAMAmdPushImageFormat.)
 // (--pipelined: XRSLAMAmdSetThreading(1), the reference's XRSLAM_ENABLE_THREADING build with deterministic hand-offs.)
 // The reference player's own command line (main.cpp:57-79) is accepted as well, so its invocations carry over:
 //
@@ -55,6 +57,7 @@ static const TruthRow *nearest_truth(const std::vector<TruthRow> &gt, double t, 
 int main(int argc, char **argv) {
     std::map<std::string, std::string> opt;
     bool undistort = true, host_undistort = false, pipelined = false, push_color = false;
+    int png_keep = PNG_GRAY;   // --push-format
     // the reference's option names (main.cpp:57-71) map onto ours
     const std::map<std::string, std::string> alias = {{"-sc", "slam"}, {"--slamconfig", "slam"}, {"-dc", "device"},
                                                       {"--deviceconfig", "device"}, {"-lc", "license"}, {"--license", "license"},
@@ -65,6 +68,16 @@ int main(int argc, char **argv) {
         else if (a == "--host-undistort") host_undistort = true;   // the reference's arrangement: the reader rectifies on the host
         else if (a == "--pipelined") pipelined = true;
         else if (a == "--push-color") push_color = true;   // colour PNGs are pushed as BGR / BGRA (channel 3 / 4): the library reduces them
+        else if (a == "--push-format" && i + 1 < argc) {
+            const std::string f = argv[++i];
+            if (f == "gray16") png_keep = PNG_KEEP_GRAY16;
+            else if (f == "rgb") png_keep = PNG_KEEP_RGB;
+            else if (f == "rgba") png_keep = PNG_KEEP_RGBA;
+            else {
+                std::fprintf(stderr, "--push-format: gray16, rgb or rgba\n");
+                return 2;
+            }
+        }
         else if (a == "-p" || a == "--play") continue;
         else if (alias.count(a) && i + 1 < argc) opt[alias.at(a)] = argv[++i];
         else if (a.rfind("--", 0) == 0 && i + 1 < argc) opt[a.substr(2)] = argv[++i];
@@ -86,7 +99,7 @@ int main(int argc, char **argv) {
     }
     if (!opt.count("slam") || !opt.count("device") || !opt.count("euroc")) {
         std::fprintf(stderr, "usage: xrslam-player --slam cfg.yaml --device sensor.yaml --euroc <dir>/mav0 [--out traj.tum] "
-                             "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color]\n"
+                             "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color] [--push-format gray16|rgb|rgba]\n"
                              "       [--view-out DIR [--view-every N] [--view-mode reference|age] [--view-trail K]]\n"
                              "   or: xrslam-player -sc cfg.yaml -dc sensor.yaml [--tum traj.tum] [--csv traj.csv] [-p] "
                              "euroc://<dir>/mav0 | tum://<dir>/mav0\n");
@@ -203,7 +216,7 @@ int main(int argc, char **argv) {
             const auto io0 = std::chrono::steady_clock::now();
             GrayImage img;
             try {
-                img = decode_png(read_file(root + "/cam0/data/" + cam[ev.index].filename), push_color);
+                img = decode_png(read_file(root + "/cam0/data/" + cam[ev.index].filename), png_keep != PNG_GRAY ? png_keep : (int)push_color);
             } catch (const std::exception &e) {
                 std::fprintf(stderr, "%s: %s\n", cam[ev.index].filename.c_str(), e.what());
                 break;
@@ -220,10 +233,13 @@ int main(int argc, char **argv) {
                 std::vector<uint8_t> g((size_t)img.w * img.h);
                 for (size_t i = 0; i < g.size(); ++i) {
                     const uint8_t *c = &img.px[i * img.channels];
-                    g[i] = (uint8_t)((c[0] * 1868 + c[1] * 9617 + c[2] * 4899 + 8192) >> 14);
+                    if (img.pixel_format == XRSLAM_AMD_PIXEL_GRAY16) g[i] = c[1];   // 16 significant bits: the high byte
+                    else if (img.pixel_format >= 0) g[i] = (uint8_t)((c[0] * 4899 + c[1] * 9617 + c[2] * 1868 + 8192) >> 14);   // RGB(A)
+                    else g[i] = (uint8_t)((c[0] * 1868 + c[1] * 9617 + c[2] * 4899 + 8192) >> 14);
                 }
                 img.px.swap(g);
                 img.channels = 1;
+                img.pixel_format = -1;
             }
             const uint8_t *pixels = img.px.data();
             if (rectify_here) {
@@ -236,14 +252,19 @@ int main(int argc, char **argv) {
                 pixels = rectified.data();
             }
             io_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - io0).count();
-            XRSLAMImage xi;
-            std::memset(&xi, 0, sizeof(xi));
-            xi.camera_id = 0;
-            xi.timeStamp = ev.t;
-            xi.data = const_cast<uint8_t *>(pixels);
-            xi.channel = img.channels;
-            xi.stride = img.w * img.channels;
-            XRSLAMPushSensorData(XRSLAM_SENSOR_CAMERA, &xi);
+            if (img.pixel_format >= 0) {
+                const XRSLAMAmdFrameFormat ff{img.pixel_format, 0, 0};
+                XRSLAMAmdPushImageFormat(pixels, img.w * img.channels, &ff, 0, ev.t);
+            } else {
+                XRSLAMImage xi;
+                std::memset(&xi, 0, sizeof(xi));
+                xi.camera_id = 0;
+                xi.timeStamp = ev.t;
+                xi.data = const_cast<uint8_t *>(pixels);
+                xi.channel = img.channels;
+                xi.stride = img.w * img.channels;
+                XRSLAMPushSensorData(XRSLAM_SENSOR_CAMERA, &xi);
+            }
             if (has_gyro && has_acc) {
                 XRSLAMRunOneFrame();
                 if (!write_view()) {   // (the frame tracked since the last image: its plane lives until the next one is tracked)

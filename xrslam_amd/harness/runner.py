@@ -58,6 +58,24 @@ class GroupStats(C.Structure):   # xrhip_group_stats (include/xrslam_hip.h)
 GROUP_KINDS = ("call", "upload", "preprocess", "track", "detect", "chain", "preint", "window_round", "window_trials", None, None, "gate")   # gate: openings / all present / timeouts
 
 
+class XRSLAMAmdFrameFormat(C.Structure):
+    _fields_ = [("format", C.c_int), ("bits", C.c_int), ("limited_range", C.c_int)]
+
+
+# XRSLAMAmdPixelFormat (include/XRSLAM.h)
+PIXEL_FORMATS = {name: i for i, name in enumerate(("gray8", "bgr8", "bgra8", "rgb8", "rgba8", "gray16", "yuyv", "uyvy", "nv12", "i420",
+                                                   "p010"))}
+
+
+def frame_format(pixel_format):
+    """'yuyv', ('gray16', 10), ('nv12', 0, 1) or numbers in their place -> XRSLAMAmdFrameFormat (format, bits, limited_range)"""
+    if isinstance(pixel_format, XRSLAMAmdFrameFormat):
+        return pixel_format
+    f = tuple(pixel_format) if isinstance(pixel_format, (tuple, list)) else (pixel_format,)
+    f = f + (0,) * (3 - len(f))
+    return XRSLAMAmdFrameFormat(PIXEL_FORMATS[f[0]] if isinstance(f[0], str) else int(f[0]), int(f[1]), int(f[2]))
+
+
 class XRSLAMAmdInitReport(C.Structure):
     _fields_ = [("attempts", C.c_long), ("successes", C.c_long), ("sfm_candidate", C.c_int),
                 ("sfm_triangulated", C.c_int), ("scale", C.c_double), ("gravity", C.c_double * 3),
@@ -85,6 +103,10 @@ def load(lib_path):
     if hasattr(lib, "XRSLAMAmdPushImageDeviceColor"):
         lib.XRSLAMAmdPushImageDeviceColor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double]
         lib.XRSLAMAmdPushImageDeviceColor.restype = None
+    have_format = hasattr(lib, "XRSLAMAmdPushImageFormat")
+    if have_format:
+        lib.XRSLAMAmdPushImageFormat.argtypes = [C.c_void_p, C.c_int, C.POINTER(XRSLAMAmdFrameFormat), C.c_int, C.c_double]
+        lib.XRSLAMAmdPushImageFormat.restype = None
     lib.XRSLAMAmdGetTimes.argtypes = [C.POINTER(XRSLAMAmdTimes)]
     lib.XRSLAMAmdGetTimes.restype = None
     lib.XRSLAMAmdLastError.restype = C.c_char_p
@@ -137,6 +159,13 @@ def load(lib_path):
             lib.XRSLAMAmdInstanceReplayColor.argtypes = [H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int,
                                                          C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p]
             lib.XRSLAMAmdInstanceReplayColor.restype = C.c_int
+        if have_format:
+            lib.XRSLAMAmdInstancePushImageFormat.argtypes = [H, C.c_void_p, C.c_int, C.POINTER(XRSLAMAmdFrameFormat), C.c_int, C.c_double]
+            lib.XRSLAMAmdInstancePushImageFormat.restype = None
+            lib.XRSLAMAmdInstanceReplayFormat.argtypes = [H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int,
+                                                          C.POINTER(XRSLAMAmdFrameFormat), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                          C.c_int, C.c_void_p]
+            lib.XRSLAMAmdInstanceReplayFormat.restype = C.c_int
     if hasattr(lib, "XRSLAMAmdGroupCreate"):
         lib.XRSLAMAmdGroupCreate.argtypes = [C.POINTER(C.c_void_p)]
         lib.XRSLAMAmdGroupDestroy.argtypes = [C.c_void_p]
@@ -197,6 +226,8 @@ class _Api:
                  "sync": ("XRSLAMAmdFlush", "XRSLAMAmdInstanceFlush")}
         if hasattr(lib, "XRSLAMAmdPushImageDeviceColor"):
             names["push_image_device_color"] = ("XRSLAMAmdPushImageDeviceColor", "XRSLAMAmdInstancePushImageDeviceColor")
+        if hasattr(lib, "XRSLAMAmdPushImageFormat"):
+            names["push_image_format"] = ("XRSLAMAmdPushImageFormat", "XRSLAMAmdInstancePushImageFormat")
         if hasattr(lib, "XRSLAMAmdRenderTrackingView"):
             names["get_features"] = ("XRSLAMAmdGetFeatures", "XRSLAMAmdInstanceGetFeatures")
             names["set_feature_history"] = ("XRSLAMAmdSetFeatureHistory", "XRSLAMAmdInstanceSetFeatureHistory")
@@ -208,12 +239,15 @@ class _Api:
 class Session:
     """One XRSLAM instance: the process singleton behind the reference's six symbols (XRSLAMManager.cpp:6-9), or --
     instance=True -- an XRSLAMAmdInstance of its own, so that several sessions can live in one process.
-    channels 3 / 4: seq["frames"] (or device_frames) hold interleaved BGR / BGRA frames, [n][h][w][channels]."""
+    channels 3 / 4: seq["frames"] (or device_frames) hold interleaved BGR / BGRA frames, [n][h][w][channels].
+    pixel_format (see frame_format): the frames are rows of bytes in that layout, [n][h][row bytes] (or [n][h][w][bytes per pixel]),
+    pushed through XRSLAMAmdPushImageFormat / XRSLAMAmdInstanceReplayFormat from host memory or from device_frames."""
 
     def __init__(self, lib_path, seq, slam_yaml=SLAM_YAML, sensor_yaml=SENSOR_YAML, device_frames=None,
-                 init_frames=60, instance=False, device_undistort=None, threading=0, group=None, channels=1):
+                 init_frames=60, instance=False, device_undistort=None, threading=0, group=None, channels=1, pixel_format=None):
         self.lib = load(lib_path)
         self.channels = int(channels)
+        self.pixel_format = None if pixel_format is None else frame_format(pixel_format)
         self.seq = seq
         cfg = C.c_void_p()
         if instance:
@@ -276,7 +310,15 @@ class Session:
             return False
         t = float(self.seq["cam_t"][self.frame_k])
         self._push_imu_until(t)
-        if self.device_frames is not None:
+        if self.pixel_format is not None:
+            if self.device_frames is not None:
+                base, fbytes, stride = self.device_frames
+                ptr, on_dev = C.c_void_p(base + self.frame_k * fbytes), 1
+            else:
+                fr = self.seq["frames"][self.frame_k]
+                ptr, stride, on_dev = C.c_void_p(fr.ctypes.data), fr.strides[0], 0
+            self.api.push_image_format(ptr, stride, C.byref(self.pixel_format), on_dev, t)
+        elif self.device_frames is not None:
             base, fbytes, stride = self.device_frames
             if self.channels == 1:
                 self.api.push_image_device(C.c_void_p(base + self.frame_k * fbytes), stride, t)
@@ -312,7 +354,11 @@ class Session:
             ptr, on_dev = C.c_void_p(base), 1
         else:
             ptr, fbytes, stride, on_dev = C.c_void_p(frames.ctypes.data), frames.strides[0], frames.strides[1], 0
-        if self.channels == 1:
+        if self.pixel_format is not None:
+            k = self.lib.XRSLAMAmdInstanceReplayFormat(self._handle, imu.ctypes.data, len(imu), cam_t.ctypes.data, len(cam_t), ptr,
+                                                       fbytes, stride, C.byref(self.pixel_format), on_dev, C.byref(ic), C.byref(fc),
+                                                       int(n), out.ctypes.data)
+        elif self.channels == 1:
             k = self.lib.XRSLAMAmdInstanceReplay(self._handle, imu.ctypes.data, len(imu), cam_t.ctypes.data, len(cam_t), ptr, fbytes,
                                                  stride, on_dev, C.byref(ic), C.byref(fc), int(n), out.ctypes.data)
         else:

@@ -46,6 +46,8 @@ def _bind():
     L.xrhip_image_upload_distorted.argtypes = [vp, vp, C.c_int, C.c_int]
     L.xrhip_image_upload_color.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.xrhip_image_upload_color_distorted.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
+    L.xrhip_image_upload_format.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.xrhip_image_upload_format_distorted.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.xrhip_debug_get_raw.argtypes = [vp, vp]
     L.xrhip_debug_set_fused_pyramid.argtypes = [vp, C.c_int]
     L.xrhip_debug_get_level_padded.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -182,6 +184,25 @@ class HipImage:
         """upload_color for a frame as the camera recorded it: reduced to gray, then rectified (KltContext.set_undistort_map)."""
         ptr, stride, channels = self._color_args(pixels, on_device, stride, channels)
         check(L().xrhip_image_upload_color_distorted(self._h, ptr, stride, channels, 1 if on_device else 0))
+
+    def _format_args(self, pixels, on_device, stride):
+        if on_device:   # pixels: a device pointer (int) to the frame's rows
+            return C.c_void_p(int(pixels)), int(stride)
+        assert pixels.dtype == np.uint8 and pixels.ndim in (2, 3) and pixels.shape[0] == self.ctx.h, pixels.shape
+        assert pixels.strides[-1] == 1 and (pixels.ndim == 2 or pixels.strides[1] == pixels.shape[2]), pixels.strides
+        return _p(pixels), pixels.strides[0]
+
+    def upload_format(self, pixels, fmt, bits=0, limited_range=0, on_device=False, stride=None):
+        """A frame in one of the XRHIP_PIXFMT_* layouts (fmt: xrslam_amd.abi.PIXFMT_*), reduced to gray on its way in: a uint8 array of the frame's
+        bytes, [h][row bytes] or [h][w][bytes per pixel] (rows may be strided), or -- on_device -- a device pointer with its row
+        stride in bytes."""
+        ptr, stride = self._format_args(pixels, on_device, stride)
+        check(L().xrhip_image_upload_format(self._h, ptr, stride, int(fmt), int(bits), int(limited_range), 1 if on_device else 0))
+
+    def upload_format_distorted(self, pixels, fmt, bits=0, limited_range=0, on_device=False, stride=None):
+        """upload_format for a frame as the camera recorded it: reduced to gray, then rectified (KltContext.set_undistort_map)."""
+        ptr, stride = self._format_args(pixels, on_device, stride)
+        check(L().xrhip_image_upload_format_distorted(self._h, ptr, stride, int(fmt), int(bits), int(limited_range), 1 if on_device else 0))
 
     def raw(self):
         """The 8-bit frame preprocess() will read (parity aid)."""
