@@ -100,8 +100,10 @@ int orc_clahe(const uint8_t *src, int w, int h, int sstride, double clip_limit,
         tw = w / tiles_x;
         th = h / tiles_y;
     } else {
-        int ew = w + (tiles_x - (w % tiles_x)) % tiles_x;
-        int eh = h + (tiles_y - (h % tiles_y)) % tiles_y;
+        /* copyMakeBorder(src, ext, 0, tilesY - rows % tilesY, 0, tilesX - cols % tilesX, BORDER_REFLECT_101): a direction
+         * that divides is extended by a whole tile count when the other one does not */
+        int ew = w + tiles_x - (w % tiles_x);
+        int eh = h + tiles_y - (h % tiles_y);
         ext = (uint8_t *)malloc((size_t)ew * eh);
         for (int y = 0; y < eh; ++y)
             for (int x = 0; x < ew; ++x)

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from oracle import klt_oracle as ko
-from tests.util import noise_image, warp_affine
+from tests.util import binarised_image, low_contrast_image, noise_image, warp_affine
 
 
 def test_reference_known_answers(golden_pair, klt_expected):
@@ -60,24 +60,33 @@ def test_reference_known_answers_at_frame_level(golden_pair, golden_pair_v1):
     assert run(golden_pair_v1) == [165, 0, 162]       # the double-rounded undistortion map is one corner off
 
 
-def _clahe_numpy(g, clip_limit=6.0, tiles=8):
-    """Independent numpy restatement of cv::CLAHE (vectorised, float32)."""
+def _clahe_numpy(g, clip_limit=6.0, tiles_x=8, tiles_y=None):
+    """Independent numpy restatement of cv::CLAHE (vectorised, float32): any tile grid, any clip limit (<= 0: no clipping;
+    the clip count is floored at 1), any frame size.  A frame that is not a multiple of the grid in BOTH directions is
+    extended to the right and below with reflect-101 by tiles - size % tiles pixels -- cv::CLAHE_Impl::apply hands exactly
+    that to copyMakeBorder, so a direction that does divide gains a whole extra pixel per tile when the other one does not."""
+    if tiles_y is None:
+        tiles_y = tiles_x
     h, w = g.shape
-    tw, th = w // tiles, h // tiles
+    ext = g
+    if w % tiles_x or h % tiles_y:
+        ext = np.pad(g, ((0, tiles_y - h % tiles_y), (0, tiles_x - w % tiles_x)), mode="reflect")
+    tw, th = ext.shape[1] // tiles_x, ext.shape[0] // tiles_y
     area = tw * th
-    clip = max(int(clip_limit * area / 256), 1)
-    lut = np.zeros((tiles, tiles, 256), np.float32)
-    for ty in range(tiles):
-        for tx in range(tiles):
-            hist = np.bincount(g[ty * th:(ty + 1) * th, tx * tw:(tx + 1) * tw].ravel(), minlength=256).astype(np.int64)
-            ex = np.maximum(hist - clip, 0).sum()
-            hist = np.minimum(hist, clip)
-            rb = ex // 256
-            res = ex - rb * 256
-            hist += rb
-            if res:
-                step = max(256 // res, 1)
-                hist[np.arange(0, 256, step)[:res]] += 1
+    clip = max(int(clip_limit * area / 256), 1) if clip_limit > 0.0 else 0
+    lut = np.zeros((tiles_y, tiles_x, 256), np.float32)
+    for ty in range(tiles_y):
+        for tx in range(tiles_x):
+            hist = np.bincount(ext[ty * th:(ty + 1) * th, tx * tw:(tx + 1) * tw].ravel(), minlength=256).astype(np.int64)
+            if clip > 0:
+                ex = np.maximum(hist - clip, 0).sum()
+                hist = np.minimum(hist, clip)
+                rb = ex // 256
+                res = ex - rb * 256
+                hist += rb
+                if res:
+                    step = max(256 // res, 1)
+                    hist[np.arange(0, 256, step)[:res]] += 1
             cs = np.cumsum(hist).astype(np.float32)
             lut[ty, tx] = np.clip(np.rint(cs * (np.float32(255.0) / np.float32(area))), 0, 255)
     x = np.arange(w, dtype=np.float32)
@@ -88,8 +97,8 @@ def _clahe_numpy(g, clip_limit=6.0, tiles=8):
     ty1 = np.floor(tyf).astype(int)
     xa = (txf - tx1.astype(np.float32))[None, :]
     ya = (tyf - ty1.astype(np.float32))[:, None]
-    tx2 = np.minimum(tx1 + 1, tiles - 1)[None, :]
-    ty2 = np.minimum(ty1 + 1, tiles - 1)[:, None]
+    tx2 = np.minimum(tx1 + 1, tiles_x - 1)[None, :]
+    ty2 = np.minimum(ty1 + 1, tiles_y - 1)[:, None]
     tx1 = np.maximum(tx1, 0)[None, :]
     ty1 = np.maximum(ty1, 0)[:, None]
     xa1 = np.float32(1) - xa
@@ -103,6 +112,24 @@ def test_clahe_matches_independent_numpy(golden_pair):
     np.testing.assert_array_equal(ko.clahe(a), _clahe_numpy(a))
     s = noise_image(640, 480, seed=3)
     np.testing.assert_array_equal(ko.clahe(s), _clahe_numpy(s))
+
+
+# (clip limit, tiles_x, tiles_y): the grid tests/test_klt_params_gpu.py runs on the device
+CLAHE_PARAMS = [(0.0, 8, 8), (0.01, 8, 8), (0.5, 3, 5), (40.0, 16, 6), (6.0, 1, 1), (6.0, 7, 3), (6.0, 64, 64), (4.0, 2, 16), (2.5, 5, 3)]
+
+
+@pytest.mark.parametrize("size", [(401, 347), (416, 352)])
+@pytest.mark.parametrize("kind", ["N", "B", "L"])
+def test_clahe_parameter_grid_matches_independent_numpy(kind, size):
+    """The oracle's CLAHE over the parameter grid of the device tests: rectangular grids, no clipping (clip 0), the clip
+    count floored at 1 (0.01), a residual >= 128, one tile for the whole frame, 4096 tiles of 7 x 6 pixels, on mid-contrast,
+    two-level and low-contrast frames.  401 x 347 divides by none of the grids, and 416 x 352 by (16, 6) in x only: the
+    case where cv::CLAHE extends the dividing direction by a whole tile count as well."""
+    w, h = size
+    g = {"N": noise_image, "B": binarised_image, "L": low_contrast_image}[kind](w, h, seed=21)
+    for clip, tx, ty in CLAHE_PARAMS:
+        np.testing.assert_array_equal(ko.clahe(g, clip, tx, ty), _clahe_numpy(g, clip, tx, ty),
+                                      err_msg="%s %dx%d clip %g tiles %dx%d" % (kind, w, h, clip, tx, ty))
 
 
 def test_pyramid_numpy_crosscheck():

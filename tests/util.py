@@ -24,6 +24,26 @@ def noise_image(w, h, seed=1, octaves=6, mean=110.0, sigma=40.0):
     return np.clip(mean + sigma * acc, 0, 255).astype(np.uint8)
 
 
+def binarised_image(w, h, seed=1):
+    """noise_image cut at its median to {0, 255}: every edge is a full-range step, so the Scharr derivatives sit at the top of their range."""
+    g = noise_image(w, h, seed)
+    return np.where(g > np.median(g), 255, 0).astype(np.uint8)
+
+
+def low_contrast_image(w, h, seed=1):
+    """noise_image squeezed to about 15 grey levels around 128: a CLAHE tile's histogram sits in a dozen bins."""
+    return noise_image(w, h, seed, mean=128.0, sigma=2.0)
+
+
+def constant_image(w, h, value):
+    return np.full((h, w), value, np.uint8)
+
+
+def shifted(img, sx, sy):
+    """The frame whose content has moved by (+sx, +sy) pixels (edge pixels repeated); whole-pixel shifts keep the grey levels."""
+    return warp_affine(img, np.eye(2), np.array([-float(sx), -float(sy)]))
+
+
 def warp_affine(img, M, t):
     """Sample img at (M @ [x,y] + t) bilinearly (inverse map), uint8 out."""
     h, w = img.shape

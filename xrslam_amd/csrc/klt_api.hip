@@ -930,7 +930,10 @@ int xrhip_image_preprocess(xrhip_image *im, double clip_limit, int tiles_x, int 
     xrhip_klt *c = im->ctx;
     const int w = c->w, h = c->h;
     if (w < 64 || h < 64) return xr_fail(XRHIP_EINVAL, "xrhip_image_preprocess: the tracker needs at least 64 pixels a side");
-    const int ew = w + (tiles_x - (w % tiles_x)) % tiles_x, eh = h + (tiles_y - (h % tiles_y)) % tiles_y;
+    // cv::CLAHE extends a frame that is not a multiple of the grid in BOTH directions by tiles - size % tiles pixels: a direction
+    // that divides gains a whole tile count when the other one does not (the tile kernel reflects whatever lies past the frame)
+    const bool divides = w % tiles_x == 0 && h % tiles_y == 0;
+    const int ew = divides ? w : w + tiles_x - w % tiles_x, eh = divides ? h : h + tiles_y - h % tiles_y;
     const int tw = ew / tiles_x, th = eh / tiles_y;
     const int tiles = tiles_x * tiles_y;
     if (tiles > c->lut_tiles) {
