@@ -186,6 +186,25 @@ typedef struct XRSLAMAmdFrameFormat {
     int limited_range;   /* 1: video levels, expanded to 0..255 */
 } XRSLAMAmdFrameFormat;
 void XRSLAMAmdPushImageFormat(const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt, int on_device, double timestamp);
+/* Frames larger than cam0.resolution.  The tracker works at the configured resolution W x H; a camera or a video decoder delivers
+ * 1280x720, 1920x1080, 3840x2160.  The crop rectangle of such a frame -- any XRSLAMAmdFrameFormat, host memory or HBM -- is cropped
+ * and area-averaged down to W x H on the GPU as part of the frame's upload, all in integers: a working pixel is the exact mean of
+ * the per-pixel gray values (format reduction first) over its footprint in the crop, rounded half up; the two axes scale
+ * independently (include/xrslam_hip.h: xrhip_image_upload_scaled has the formula).  `pixels` is row 0 of the source frame, `stride`
+ * its row pitch in bytes; only the crop's bytes are read, and of a host frame only the crop crosses the host link.
+ * Required: the crop inside the source, W <= crop_width, H <= crop_height (no upscaling), crop_width * crop_height <= 2^24,
+ * stride >= src_width * bytes per pixel.  A bad geometry drops the frame and sets XRSLAMAmdLastError; nothing aborts.
+ * cam0.intrinsics / distortion / resolution describe the WORKING image, as always: with device undistortion on the frame is scaled
+ * first and rectified second, and the library does not rewrite the configuration.  XRSLAMAmdScaleIntrinsics maps the source
+ * camera's {fx, fy, cx, cy} through a geometry (pixel centres at integer coordinates): fx' = fx*W/cw, fy' = fy*H/ch,
+ * cx' = (cx + 0.5 - crop_x)*W/cw - 0.5, cy' = (cy + 0.5 - crop_y)*H/ch - 0.5; distortion coefficients are unchanged. */
+typedef struct XRSLAMAmdFrameGeometry {
+    int src_width, src_height;                      /* the frame as it lies in memory */
+    int crop_x, crop_y, crop_width, crop_height;    /* the rectangle that becomes the working image */
+} XRSLAMAmdFrameGeometry;
+void XRSLAMAmdPushImageScaled(const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt /* NULL = GRAY8 */,
+                              const XRSLAMAmdFrameGeometry *geo, int on_device, double timestamp);
+void XRSLAMAmdScaleIntrinsics(const double src[4], const XRSLAMAmdFrameGeometry *geo, int W, int H, double out[4]);
 /* What the reference's dataset readers ask the YamlConfig* for (xrslam-pc/player/src/IO/euroc_dataset_reader.cpp:4-7,16,62-66;
  * tum_dataset_reader.cpp:4-6,67-76): camera_time_offset(), camera_distortion_flag(), camera_distortion(),
  * camera_intrinsic(), camera_resolution().  The `config` out-parameter of XRSLAMCreate is an opaque handle here (the
@@ -318,6 +337,8 @@ void XRSLAMAmdInstancePushImageDeviceColor(XRSLAMAmdInstance *inst, const void *
                                            double timestamp);
 void XRSLAMAmdInstancePushImageFormat(XRSLAMAmdInstance *inst, const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt,
                                       int on_device, double timestamp);
+void XRSLAMAmdInstancePushImageScaled(XRSLAMAmdInstance *inst, const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt,
+                                      const XRSLAMAmdFrameGeometry *geo, int on_device, double timestamp);
 void XRSLAMAmdInstanceGetCameraConfig(XRSLAMAmdInstance *inst, XRSLAMAmdCameraConfig *out);
 int XRSLAMAmdInstanceDescribeConfig(XRSLAMAmdInstance *inst, char *buf, int cap);
 void XRSLAMAmdInstanceSetDeviceUndistort(XRSLAMAmdInstance *inst, const char *model);
@@ -367,6 +388,12 @@ int XRSLAMAmdInstanceReplayColor(XRSLAMAmdInstance *inst, const double *imu7, in
 int XRSLAMAmdInstanceReplayFormat(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
                                   const void *frames, size_t frame_bytes, int stride, const XRSLAMAmdFrameFormat *fmt, int on_device,
                                   int *imu_cursor, int *frame_cursor, int n_steps, double *poses_out8);
+/* The same loop over frames larger than cam0.resolution (XRSLAMAmdPushImageScaled): frame_bytes, stride and geo describe the
+ * frames as they lie in memory; fmt NULL = GRAY8. */
+int XRSLAMAmdInstanceReplayScaled(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
+                                  const void *frames, size_t frame_bytes, int stride, const XRSLAMAmdFrameFormat *fmt,
+                                  const XRSLAMAmdFrameGeometry *geo, int on_device, int *imu_cursor, int *frame_cursor, int n_steps,
+                                  double *poses_out8);
 
 #ifdef __cplusplus
 }

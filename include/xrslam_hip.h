@@ -127,6 +127,33 @@ int xrhip_image_upload_format(xrhip_image *img, const void *pixels, int stride_b
                               int on_device);
 int xrhip_image_upload_format_distorted(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits,
                                         int limited_range, int on_device);
+/* Frames larger than the context's plane: the crop rectangle of a src_width x src_height frame of any XRHIP_PIXFMT_* is cropped and
+ * area-averaged down to the W x H working plane (xrhip_klt_create's size) as part of its upload.  All integer.  g(i, j) is the
+ * per-pixel gray value of source pixel (i, j) of the crop as defined above (format, bits, limited_range, applied per source pixel
+ * before averaging).  In units where a source pixel is W wide, plane pixel X spans [X*cw, (X+1)*cw) and source column i covers
+ * [i*W, (i+1)*W); a_i is the overlap of the two (the a_i sum to cw = crop_width), b_j the same vertically with ch = crop_height and H:
+ *   out(X, Y) = (sum_j b_j sum_i a_i g(i, j) + cw*ch / 2) / (cw*ch)      -- the exact area mean, rounded half up.
+ * cw == W and ch == H: a plain crop; an integer ratio k: the k x k box mean; the axes scale independently.  In real arithmetic this
+ * is cv::resize(INTER_AREA); OpenCV works in float, no bit parity with it is claimed.
+ * Requirements (XRHIP_EINVAL, the message names the argument): non-null img / pixels / geo; the crop inside the source;
+ * W <= crop_width and H <= crop_height (no upscaling); crop_width * crop_height <= 2^24; stride_bytes >= src_width * bytes per
+ * pixel; the format rules above.  A bad call leaves the image as it was.
+ * `pixels`: row 0 of the SOURCE frame, host or HBM (on_device), any alignment.  Needed bytes: rows crop_y .. crop_y + ch - 1, bytes
+ * crop_x * bpp .. (crop_x + cw) * bpp - 1 of each; the device reads whole aligned dwords, each of which holds a needed byte -- nothing
+ * outside the crop need exist.  A host frame is free on return; only its crop crosses the host link, once.
+ * _distorted: scaled first, rectified second -- the undistortion map describes the WORKING image (XRHIP_ESTATE without a map).
+ * A member of a group: a launch of its own in the member's order (like the undistortion remap), results as in a solo run. */
+typedef struct xrhip_frame_geometry {
+    int src_width, src_height;
+    int crop_x, crop_y, crop_width, crop_height;
+} xrhip_frame_geometry;
+int xrhip_image_upload_scaled(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits, int limited_range,
+                              int on_device, const xrhip_frame_geometry *geo);
+int xrhip_image_upload_scaled_distorted(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits, int limited_range,
+                                        int on_device, const xrhip_frame_geometry *geo);
+/* measurement aid: HIP-event time, in ms, of what the context issues between a call with phase 0 and one with phase 1 (each waits
+ * for the context's queue; `ms` is written by phase 1) */
+int xrhip_debug_stream_span(xrhip_klt *ctx, int phase, double *ms);
 /* parity aid: the 8-bit frame xrhip_image_preprocess will read */
 int xrhip_debug_get_raw(xrhip_image *img, uint8_t *out);
 /* Development / parity aids of the pyramid build (xrhip_image_preprocess): on = 1 (default) builds the CLAHE plane, the three

@@ -175,3 +175,9 @@ PIXFMT_GRAY8, PIXFMT_BGR8, PIXFMT_BGRA8, PIXFMT_RGB8, PIXFMT_RGBA8, PIXFMT_GRAY1
     PIXFMT_I420, PIXFMT_P010 = range(11)
 PIXFMT_BYTES = {PIXFMT_GRAY8: 1, PIXFMT_BGR8: 3, PIXFMT_BGRA8: 4, PIXFMT_RGB8: 3, PIXFMT_RGBA8: 4, PIXFMT_GRAY16: 2, PIXFMT_YUYV: 2,
                 PIXFMT_UYVY: 2, PIXFMT_NV12: 1, PIXFMT_I420: 1, PIXFMT_P010: 2}   # bytes per pixel read (NV12 / I420 / P010: the luma plane's)
+
+
+class FrameGeometry(C.Structure):
+    """xrhip_frame_geometry = XRSLAMAmdFrameGeometry: the crop of a src_width x src_height frame that becomes the working image"""
+    _fields_ = [("src_width", C.c_int), ("src_height", C.c_int), ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int),
+                ("crop_height", C.c_int)]

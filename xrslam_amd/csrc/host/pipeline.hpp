@@ -55,6 +55,9 @@ int xrhip_image_upload_color_distorted(xrhip_image *img, const void *pixels, int
 // (likewise the uploads of the other pixel formats: Pipeline::make_image reduces such frames with pixel_format.hpp's formulas)
 int xrhip_image_upload_format(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits, int limited_range, int on_device) __attribute__((weak));
 int xrhip_image_upload_format_distorted(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits, int limited_range, int on_device) __attribute__((weak));
+// (likewise the scaled uploads: Pipeline::make_image crops and area-averages such frames with pixel_format.hpp's scale_frame)
+int xrhip_image_upload_scaled(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits, int limited_range, int on_device, const xrhip_frame_geometry *geo) __attribute__((weak));
+int xrhip_image_upload_scaled_distorted(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits, int limited_range, int on_device, const xrhip_frame_geometry *geo) __attribute__((weak));
 // (likewise the tracking view's renderer: the feature snapshot below needs nothing of it)
 int xrhip_image_render_view(xrhip_image *img, const xrhip_view_segment *segs, int n_segs, const xrhip_view_marker *markers, int n_markers,
                             const uint8_t *palette_bgr, int n_palette, void *out, int stride_bytes, int channels, int on_device) __attribute__((weak));
@@ -62,6 +65,7 @@ int xrhip_image_render_view(xrhip_image *img, const xrhip_view_segment *segs, in
 
 namespace xrh {
 inline bool have_format_upload() { return xrhip_image_upload_format != nullptr && xrhip_image_upload_format_distorted != nullptr; }
+inline bool have_scaled_upload() { return xrhip_image_upload_scaled != nullptr && xrhip_image_upload_scaled_distorted != nullptr; }
 inline bool have_color_upload() { return xrhip_image_upload_color != nullptr && xrhip_image_upload_color_distorted != nullptr; }
 
 struct HipError : std::runtime_error {
@@ -316,10 +320,35 @@ struct Pipeline {
     static constexpr int NO_PIXEL_FORMAT = INT_MIN;
     std::vector<uint8_t> gray_scratch;
     std::shared_ptr<HipImage> make_image(const uint8_t *gray, int stride, double t, bool device_ptr, int channels = 1, int format = NO_PIXEL_FORMAT,
-                                         int bits = 0, int limited_range = 0) {
+                                         int bits = 0, int limited_range = 0, const xrhip_frame_geometry *geo = nullptr) {
         const int cols = (int)config.cam_resolution[0], rows = (int)config.cam_resolution[1];
         PixelFormat pf;
         bool by_format = false;
+        // geo: the frame is larger than cam_resolution -- its crop is area-averaged down to the working plane by
+        // xrhip_image_upload_scaled (any format), or here with the same integers where the library has no such upload; what follows
+        // then sees the working-size gray frame
+        bool scaled = false;
+        int scaled_format = XRHIP_PIXFMT_GRAY8;
+        if (geo) {
+            if (format == NO_PIXEL_FORMAT) format = XRHIP_PIXFMT_GRAY8;
+            if (const char *why = describe_pixel_format(format, bits, limited_range, pf))
+                throw std::runtime_error(std::string("Image format is not supported: ") + why);
+            if (!gray) throw std::runtime_error("Image geometry is not supported: null pixels");
+            if (const char *why = check_frame_geometry(geo, cols, rows, pf.bpp, stride))
+                throw std::runtime_error(std::string("Image geometry is not supported: ") + why);
+            if (have_scaled_upload()) {
+                scaled = true;
+            } else {
+                if (device_ptr) throw std::runtime_error("Image geometry is not supported: this library cannot scale a frame in device memory");
+                gray_scratch.resize((size_t)cols * rows);
+                scale_frame(gray_scratch.data(), cols, rows, crop_origin(gray, stride, *geo, pf.bpp), stride, geo->crop_width, geo->crop_height, pf);
+                gray = gray_scratch.data();
+                stride = cols;
+            }
+            scaled_format = format;
+            format = NO_PIXEL_FORMAT;
+            channels = 1;
+        }
         if (format != NO_PIXEL_FORMAT) {
             if (const char *why = describe_pixel_format(format, bits, limited_range, pf))
                 throw std::runtime_error(std::string("Image format is not supported: ") + why);
@@ -347,7 +376,11 @@ struct Pipeline {
         }
         // a member of an instance group starts its frame together with the other members (timing only: xrslam_hip.h, frame gate)
         if (group) xrhip_klt_frame_gate(klt);
-        if (by_format) {
+        if (scaled) {
+            if (undistort_on_device)
+                hip_check(xrhip_image_upload_scaled_distorted(img->h, gray, stride, scaled_format, bits, limited_range, device_ptr ? 1 : 0, geo), "xrhip_image_upload_scaled_distorted");
+            else hip_check(xrhip_image_upload_scaled(img->h, gray, stride, scaled_format, bits, limited_range, device_ptr ? 1 : 0, geo), "xrhip_image_upload_scaled");
+        } else if (by_format) {
             if (undistort_on_device)
                 hip_check(xrhip_image_upload_format_distorted(img->h, gray, stride, format, bits, limited_range, device_ptr ? 1 : 0), "xrhip_image_upload_format_distorted");
             else hip_check(xrhip_image_upload_format(img->h, gray, stride, format, bits, limited_range, device_ptr ? 1 : 0), "xrhip_image_upload_format");

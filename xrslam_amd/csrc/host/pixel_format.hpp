@@ -77,4 +77,68 @@ inline void pack_rows(uint8_t *dst, const uint8_t *src, int stride, size_t row_b
     for (int y = 0; y < rows; ++y) std::memcpy(dst + (size_t)y * row_bytes, src + (size_t)y * stride, row_bytes);
 }
 
+// ------------------------------------------------------------------------------------------------ frames larger than the working plane
+// A frame geometry (xrslam_hip.h: xrhip_frame_geometry): the crop {crop_x, crop_y, cw, ch} of a src_width x src_height frame is
+// area-averaged down to the W x H working plane.  Destination pixel (X, Y) is the exact mean of the per-pixel gray values over its
+// footprint, rounded half up: in units where a source pixel is W wide the destination pixel spans [X*cw, (X+1)*cw), source column i
+// covers [i*W, (i+1)*W), a_i is their overlap (the a_i sum to cw); b_j likewise with ch and H;
+//   out = (sum_j b_j sum_i a_i g(i, j) + cw*ch / 2) / (cw*ch)
+// cw*ch <= 2^24 keeps 255*cw*ch + cw*ch/2 inside 32 bits.  Plain C++, all integer: the device kernel (k_upload_scaled) and the numpy
+// model (tests/scale_model.py) give the same bits.
+constexpr long long SCALE_MAX_CROP_AREA = 1ll << 24;
+
+// nullptr, or which argument is wrong and why
+inline const char *check_frame_geometry(const xrhip_frame_geometry *g, int W, int H, int bpp, long long stride) {
+    if (!g) return "geo is null";
+    if (g->src_width < 1 || g->src_height < 1) return "geo: src_width and src_height must be positive";
+    if (g->crop_width < 1 || g->crop_height < 1 || g->crop_x < 0 || g->crop_y < 0 ||
+        (long long)g->crop_x + g->crop_width > g->src_width || (long long)g->crop_y + g->crop_height > g->src_height)
+        return "geo: the crop rectangle lies outside the source frame";
+    if (g->crop_width < W) return "geo: crop_width is smaller than the working width (no upscaling)";
+    if (g->crop_height < H) return "geo: crop_height is smaller than the working height (no upscaling)";
+    if ((long long)g->crop_width * g->crop_height > SCALE_MAX_CROP_AREA) return "geo: crop_width * crop_height exceeds 2^24";
+    if (stride < (long long)g->src_width * bpp) return "stride_bytes < src_width * bytes per pixel";
+    return nullptr;
+}
+
+// The crop's first byte in a frame whose row 0 starts at `pixels`
+inline const uint8_t *crop_origin(const uint8_t *pixels, long long stride, const xrhip_frame_geometry &g, int bpp) {
+    return pixels + (size_t)g.crop_y * (size_t)stride + (size_t)g.crop_x * bpp;
+}
+
+// `src`: the crop's first byte (rows `stride` bytes apart, cw x ch pixels of f.bpp bytes) -> the dense W x H plane `dst`.  Reads the
+// cw * f.bpp bytes of each of the ch rows and nothing else.
+inline void scale_frame(uint8_t *dst, int W, int H, const uint8_t *src, long long stride, int cw, int ch, const PixelFormat &f) {
+    const uint32_t area = (uint32_t)cw * (uint32_t)ch, half = area / 2;
+    for (int Y = 0; Y < H; ++Y) {
+        const long long y0 = (long long)Y * ch, y1 = y0 + ch;
+        const int j0 = (int)(y0 / H), j1 = (int)((y1 + H - 1) / H);
+        for (int X = 0; X < W; ++X) {
+            const long long x0 = (long long)X * cw, x1 = x0 + cw;
+            const int i0 = (int)(x0 / W), i1 = (int)((x1 + W - 1) / W);
+            uint32_t acc = 0;
+            for (int j = j0; j < j1; ++j) {
+                const uint32_t b = (uint32_t)(std::min<long long>((long long)(j + 1) * H, y1) - std::max<long long>((long long)j * H, y0));
+                const uint8_t *row = src + (size_t)j * (size_t)stride;
+                uint32_t r = 0;
+                for (int i = i0; i < i1; ++i) {
+                    const uint32_t a = (uint32_t)(std::min<long long>((long long)(i + 1) * W, x1) - std::max<long long>((long long)i * W, x0));
+                    r += a * reduce_pixel(row + (size_t)i * f.bpp, f);
+                }
+                acc += b * r;
+            }
+            dst[(size_t)Y * W + X] = (uint8_t)((acc + half) / area);
+        }
+    }
+}
+
+// Intrinsics {fx, fy, cx, cy} of the source frame -> those of the W x H working plane, pixel centres at integer coordinates:
+// a source coordinate u maps to (u + 0.5 - crop_x) * W / cw - 0.5.  Distortion coefficients act on normalised coordinates: unchanged.
+inline void scale_intrinsics(const double src[4], const xrhip_frame_geometry &g, int W, int H, double out[4]) {
+    const double sx = (double)W / g.crop_width, sy = (double)H / g.crop_height;
+    const double fx = src[0] * sx, fy = src[1] * sy;
+    const double cx = (src[2] + 0.5 - g.crop_x) * sx - 0.5, cy = (src[3] + 0.5 - g.crop_y) * sy - 0.5;
+    out[0] = fx; out[1] = fy; out[2] = cx; out[3] = cy;
+}
+
 }   // namespace xrh

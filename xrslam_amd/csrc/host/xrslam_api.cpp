@@ -266,6 +266,30 @@ void impl_push_image_format(Manager &m, const void *pixels, int stride, const XR
     });
 }
 
+// A frame larger than the working resolution (XRSLAMAmdFrameGeometry), of any format (null: GRAY8).  A bad geometry or format drops
+// the frame and sets the last error.
+xrhip_frame_geometry to_inner(const XRSLAMAmdFrameGeometry &g) {
+    return xrhip_frame_geometry{g.src_width, g.src_height, g.crop_x, g.crop_y, g.crop_width, g.crop_height};
+}
+void impl_push_image_scaled(Manager &m, const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt, const XRSLAMAmdFrameGeometry *geo,
+                            int on_device, double timestamp) {
+    if (!m.sys) return;
+    bind_device(m);
+    guarded(m, [&] {
+        try {
+            std::lock_guard<std::mutex> lk(m.input_mutex);
+            if (!geo || !pixels) throw std::runtime_error("Image geometry is not supported: null pixels or geometry");
+            const xrhip_frame_geometry g = to_inner(*geo);
+            m.cur_image = m.sys->P.make_image(static_cast<const uint8_t *>(pixels), stride, timestamp, on_device != 0, 1,
+                                              fmt ? fmt->format : (int)XRSLAM_AMD_PIXEL_GRAY8, fmt ? fmt->bits : 0, fmt ? fmt->limited_range : 0, &g);
+        } catch (...) {
+            std::lock_guard<std::mutex> lk(m.input_mutex);
+            m.cur_image.reset();
+            throw;
+        }
+    });
+}
+
 void impl_get_camera_config(Manager &m, XRSLAMAmdCameraConfig *out) {
     if (!out) return;
     std::memset(out, 0, sizeof(*out));
@@ -474,6 +498,14 @@ void XRSLAMAmdPushImageDevice(const void *gray_dev, int stride, double timestamp
 void XRSLAMAmdPushImageDeviceColor(const void *pixels_dev, int stride, int channels, double timestamp) {
     impl_push_image_device(mgr(), pixels_dev, stride, timestamp, channels);
 }
+void XRSLAMAmdPushImageScaled(const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt, const XRSLAMAmdFrameGeometry *geo,
+                              int on_device, double timestamp) {
+    impl_push_image_scaled(mgr(), pixels, stride, fmt, geo, on_device, timestamp);
+}
+void XRSLAMAmdScaleIntrinsics(const double src[4], const XRSLAMAmdFrameGeometry *geo, int W, int H, double out[4]) {
+    if (!src || !geo || !out || W < 1 || H < 1 || geo->crop_width < 1 || geo->crop_height < 1) return;
+    xrh::scale_intrinsics(src, to_inner(*geo), W, H, out);
+}
 void XRSLAMAmdPushImageFormat(const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt, int on_device, double timestamp) {
     impl_push_image_format(mgr(), pixels, stride, fmt, on_device, timestamp);
 }
@@ -534,6 +566,10 @@ void XRSLAMAmdInstancePushImageDevice(XRSLAMAmdInstance *inst, const void *gray_
 void XRSLAMAmdInstancePushImageDeviceColor(XRSLAMAmdInstance *inst, const void *pixels_dev, int stride, int channels,
                                            double timestamp) {
     if (inst) impl_push_image_device(inst->m, pixels_dev, stride, timestamp, channels);
+}
+void XRSLAMAmdInstancePushImageScaled(XRSLAMAmdInstance *inst, const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt,
+                                      const XRSLAMAmdFrameGeometry *geo, int on_device, double timestamp) {
+    if (inst) impl_push_image_scaled(inst->m, pixels, stride, fmt, geo, on_device, timestamp);
 }
 void XRSLAMAmdInstancePushImageFormat(XRSLAMAmdInstance *inst, const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt,
                                       int on_device, double timestamp) {
@@ -628,10 +664,10 @@ void XRSLAMAmdGroupGetStats(XRSLAMAmdGroup *grp, void *out, int reset) {
 // The player's loop (xrslam-pc/player/src/main.cpp:116-169) for n_steps camera frames of a pre-staged sequence, without a
 // host-language round trip per sensor sample: at equal timestamps gyroscope, then accelerometer, then camera
 // (IO/async_dataset_reader.cpp:41-48); RunOneFrame and the state / pose query after every image.
-// (fmt: the frames' XRSLAMAmdFrameFormat, or null for `channels`)
+// (fmt: the frames' XRSLAMAmdFrameFormat, or null for `channels`; geo: frames larger than the working resolution)
 static int replay(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames, const void *frames,
                   size_t frame_bytes, int stride, int channels, const XRSLAMAmdFrameFormat *fmt, int on_device, int *imu_cursor,
-                  int *frame_cursor, int n_steps, double *poses_out8) {
+                  int *frame_cursor, int n_steps, double *poses_out8, const XRSLAMAmdFrameGeometry *geo = nullptr) {
     if (!inst || !imu7 || !cam_t || !frames || !imu_cursor || !frame_cursor) return -1;
     Manager &m = inst->m;
     int n_poses = 0;
@@ -658,7 +694,9 @@ static int replay(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const 
         }
         *imu_cursor = k;
         const unsigned char *img = static_cast<const unsigned char *>(frames) + (size_t)fk * frame_bytes;
-        if (fmt) {
+        if (geo) {
+            impl_push_image_scaled(m, img, stride, fmt, geo, on_device, t);
+        } else if (fmt) {
             impl_push_image_format(m, img, stride, fmt, on_device, t);
         } else if (on_device) {
             impl_push_image_device(m, img, stride, t, channels);
@@ -701,6 +739,15 @@ int XRSLAMAmdInstanceReplayFormat(XRSLAMAmdInstance *inst, const double *imu7, i
     if (!fmt) return -1;
     return replay(inst, imu7, n_imu, cam_t, n_frames, frames, frame_bytes, stride, 1, fmt, on_device, imu_cursor, frame_cursor, n_steps,
                   poses_out8);
+}
+
+int XRSLAMAmdInstanceReplayScaled(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
+                                  const void *frames, size_t frame_bytes, int stride, const XRSLAMAmdFrameFormat *fmt,
+                                  const XRSLAMAmdFrameGeometry *geo, int on_device, int *imu_cursor, int *frame_cursor, int n_steps,
+                                  double *poses_out8) {
+    if (!geo) return -1;
+    return replay(inst, imu7, n_imu, cam_t, n_frames, frames, frame_bytes, stride, 1, fmt, on_device, imu_cursor, frame_cursor, n_steps,
+                  poses_out8, geo);
 }
 
 int XRSLAMAmdInstanceReplay(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,

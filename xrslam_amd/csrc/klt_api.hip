@@ -134,6 +134,11 @@ struct xrhip_klt {
     bool view_timing = false;
     double view_ms = 0;
     long long view_n = 0;
+    // frames larger than the plane (xrhip_image_upload_scaled): the crop of a host frame in HBM, where k_upload_scaled reads it.
+    // Nothing of it exists before the first scaled upload of a host frame.
+    uint8_t *scale_src = nullptr;
+    size_t scale_cap = 0;
+    hipEvent_t span_t0 = nullptr, span_t1 = nullptr;   // xrhip_debug_stream_span
 };
 
 struct xrhip_image {
@@ -546,6 +551,9 @@ void xrhip_klt_destroy(xrhip_klt *c) {
     if (c->view_done) hipEventDestroy(c->view_done);
     if (c->view_t0) hipEventDestroy(c->view_t0);
     if (c->view_t1) hipEventDestroy(c->view_t1);
+    hipFree(c->scale_src);
+    if (c->span_t0) hipEventDestroy(c->span_t0);
+    if (c->span_t1) hipEventDestroy(c->span_t1);
     for (int i = 0; i < xrhip_klt::UP_SLOTS; ++i) {
         hipHostFree(c->up_buf[i]);
         if (c->up_done[i]) hipEventDestroy(c->up_done[i]);
@@ -921,6 +929,146 @@ int xrhip_image_upload_format_distorted(xrhip_image *im, const void *pixels, int
     rc = upload_color_into(c, pixels, stride, pf.bpp, on_device, c->undist_src, fmt);   // reduced first, rectified second
     if (rc) return rc;
     return xrhip_image_upload_distorted(im, c->undist_src, c->w, 1);
+}
+
+// ---------------------------------------------------------------------------------------------- frames larger than the working plane
+// The crop of a frame of any pixel format, area-averaged down to the context's plane (k_upload_scaled) on the way in.  A frame in HBM
+// is read where it lies.  A host frame: only the crop is staged (rows of cw * bpp bytes, packed) through the pinned slots, which grow
+// as they do for colour; the slot is then copied to an HBM scratch and the kernel reads that.  Neighbouring plane pixels share
+// source pixels and a plane row's footprint rows are read by several wavefronts, so a kernel reading the mapped slot would fetch
+// bytes over the host link more than once unless every repeat hit a cache -- nothing guarantees that for host memory; the copy costs
+// one HBM write and read of the crop and makes "once over the link" hold by construction.
+// Not part of the shared upload launch: like the undistortion remap it is a launch of its own, in the context's order (a group
+// member: on the group's front-end queue, behind a pending upload, which is submitted first).
+static int check_scaled_args(const char *who, const xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited,
+                             const xrhip_frame_geometry *geo, xrh::PixelFormat &pf) {
+    if (!im) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": img is null").c_str());
+    if (!pixels) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": pixels is null").c_str());
+    if (const char *why = xrh::describe_pixel_format(format, bits, limited, pf)) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": " + why).c_str());
+    if (const char *why = xrh::check_frame_geometry(geo, im->ctx->w, im->ctx->h, pf.bpp, stride)) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": " + why).c_str());
+    return XRHIP_OK;
+}
+static int upload_scaled_into(xrhip_klt *c, const void *pixels, int stride, const xrh::PixelFormat &pf, int on_device,
+                              const xrhip_frame_geometry &g, uint8_t *dst) {
+    const int cw = g.crop_width, ch = g.crop_height;
+    const uint8_t *origin = xrh::crop_origin(static_cast<const uint8_t *>(pixels), stride, g, pf.bpp);
+    ScaleArgs a{};
+    a.dst = dst;
+    a.w = c->w;
+    a.h = c->h;
+    a.bpp = pf.bpp;
+    a.fmt = upf_word(pf);
+    a.cw = cw;
+    a.ch = ch;
+    a.wide = ((uint64_t)c->w * (uint64_t)cw >> 32) != 0 || ((uint64_t)c->h * (uint64_t)ch >> 32) != 0;
+    const unsigned n4 = (unsigned)(((size_t)c->w * c->h + 3) / 4);
+    const dim3 grid(std::max(1u, std::min((n4 + 255u) / 256u, 2048u)));
+    if (on_device) {
+        a.src = origin;
+        a.sstride = stride;
+        return klt_run(c, [=](hipStream_t st) {
+            hipLaunchKernelGGL(k_upload_scaled, grid, dim3(256), 0, st, a);
+            XR_HIP(hipGetLastError());
+            return XRHIP_OK;
+        });
+    }
+    const size_t row = (size_t)cw * pf.bpp, bytes = row * ch;
+    int rc = ensure_slot_bytes(c, bytes);
+    if (rc) return rc;
+    if (bytes > c->scale_cap) {
+        // nothing may still be reading the scratch that is about to go
+        if (c->group) {
+            rc = flush_upload(c);
+            if (rc) return rc;
+            rc = group_drain(c->group, GQ_KLT, c);
+            if (rc) return rc;
+            c->uploads_unsynced = 0;
+        } else {
+            XR_HIP(hipStreamSynchronize(c->stream));
+        }
+        hipFree(c->scale_src);
+        c->scale_src = nullptr;
+        c->scale_cap = 0;
+        XR_HIP(hipMalloc(&c->scale_src, bytes));
+        c->scale_cap = bytes;
+    }
+    const int slot = c->up_next;
+    c->up_next = (slot + 1) % xrhip_klt::UP_SLOTS;
+    if (c->group) {   // (the slots' reuse: as in stage_host_frame)
+        if (c->uploads_unsynced >= xrhip_klt::UP_SLOTS - 1) {
+            rc = group_drain(c->group, GQ_KLT, c);
+            if (rc) return rc;
+            c->uploads_unsynced = 0;
+        }
+    } else if (c->up_busy[slot]) {
+        XR_HIP(hipEventSynchronize(c->up_done[slot]));
+    }
+    uint8_t *buf = c->up_buf[slot];
+    if ((size_t)stride == row) copy_to_pinned(buf, origin, bytes);
+    else xrh::pack_rows(buf, origin, stride, row, ch);
+    a.src = c->scale_src;
+    a.sstride = (int)row;
+    rc = klt_run(c, [=](hipStream_t st) {
+        XR_HIP(hipMemcpyAsync(c->scale_src, buf, bytes, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_upload_scaled, grid, dim3(256), 0, st, a);
+        XR_HIP(hipGetLastError());
+        return XRHIP_OK;
+    });
+    if (rc) return rc;
+    if (c->group) {
+        c->uploads_unsynced++;
+    } else {
+        XR_HIP(hipEventRecord(c->up_done[slot], c->stream));
+        c->up_busy[slot] = true;
+    }
+    return XRHIP_OK;
+}
+
+int xrhip_image_upload_scaled(xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited, int on_device,
+                              const xrhip_frame_geometry *geo) {
+    xrh::PixelFormat pf;
+    int rc = check_scaled_args("xrhip_image_upload_scaled", im, pixels, stride, format, bits, limited, geo, pf);
+    if (rc) return rc;
+    rc = upload_scaled_into(im->ctx, pixels, stride, pf, on_device, *geo, im->raw);
+    if (rc) return rc;
+    im->have_raw = true;
+    im->have_pyramid = false;
+    im->want_detect = false;
+    im->detect_seq = 0;
+    return XRHIP_OK;
+}
+
+int xrhip_image_upload_scaled_distorted(xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited, int on_device,
+                                        const xrhip_frame_geometry *geo) {
+    xrh::PixelFormat pf;
+    int rc = check_scaled_args("xrhip_image_upload_scaled_distorted", im, pixels, stride, format, bits, limited, geo, pf);
+    if (rc) return rc;
+    xrhip_klt *c = im->ctx;
+    if (!c->have_undist) return xr_fail(XRHIP_ESTATE, "xrhip_image_upload_scaled_distorted: no undistortion map (xrhip_klt_set_undistort_map)");
+    rc = upload_scaled_into(c, pixels, stride, pf, on_device, *geo, c->undist_src);   // scaled first, rectified second
+    if (rc) return rc;
+    return xrhip_image_upload_distorted(im, c->undist_src, c->w, 1);
+}
+
+/* measurement aid: HIP-event time of whatever the context issues between phase 0 and phase 1 (which waits for it) */
+int xrhip_debug_stream_span(xrhip_klt *c, int phase, double *ms) {
+    if (!c || (phase != 0 && phase != 1)) return xr_fail(XRHIP_EINVAL, "xrhip_debug_stream_span: bad arguments");
+    if (!c->span_t0) {
+        XR_HIP(hipEventCreate(&c->span_t0));
+        XR_HIP(hipEventCreate(&c->span_t1));
+    }
+    hipEvent_t e = phase ? c->span_t1 : c->span_t0;
+    int rc = klt_run_sync(c, [=](hipStream_t st) {
+        XR_HIP(hipEventRecord(e, st));
+        return XRHIP_OK;
+    });
+    if (rc) return rc;
+    if (phase && ms) {
+        float f = 0.f;
+        XR_HIP(hipEventElapsedTime(&f, c->span_t0, c->span_t1));
+        *ms = f;
+    }
+    return XRHIP_OK;
 }
 
 int xrhip_image_preprocess(xrhip_image *im, double clip_limit, int tiles_x, int tiles_y) {

@@ -1531,6 +1531,142 @@ __global__ __launch_bounds__(256) void k_upload(Batch<UploadArgs> b) {
     }
 }
 
+// ------------------------------------------------------------------------------- frames larger than the plane (xrhip_image_upload_scaled)
+// The crop of a larger frame, area-averaged down to the dense w x h plane as part of its upload.  `src` is the crop's first byte: cw x
+// ch pixels of bpp bytes, rows sstride apart; the gray value of a source pixel is the per-pixel reduction above (bpp, fmt).  All
+// integer (host/pixel_format.hpp: scale_frame is the same arithmetic): in units where a source pixel is w wide, plane pixel X spans
+// [X*cw, (X+1)*cw) and source column i covers [i*w, (i+1)*w); a_i is their overlap, b_j the same vertically with ch and h;
+//   out = (sum_j b_j sum_i a_i g(i, j) + cw*ch / 2) / (cw*ch),   cw*ch <= 2^24: every sum stays inside 32 bits.
+struct ScaleArgs {
+    const uint8_t *src;
+    int sstride;
+    uint8_t *dst;   // dense w x h
+    int w, h;
+    int bpp, fmt;   // as UploadArgs
+    int cw, ch;     // w <= cw, h <= ch
+    int wide;       // w * cw or h * ch does not fit 32 bits: the footprint's first column / row is computed in 64
+};
+// x * m = q * d + r
+__device__ __forceinline__ void scale_muldiv(uint32_t x, uint32_t m, uint32_t d, bool wide, uint32_t &q, uint32_t &r) {
+    if (wide) {
+        const uint64_t p = (uint64_t)x * m, qq = p / d;
+        q = (uint32_t)qq;
+        r = (uint32_t)(p - qq * d);
+    } else {
+        const uint32_t p = x * m;
+        q = p / d;
+        r = p - q * d;
+    }
+}
+// the gray values of the four source pixels in the BPP dwords `d` (d_upload_reduce's unpacking)
+template <int BPP> __device__ __forceinline__ void scale_gray4(const uint32_t (&d)[BPP + 1], uint32_t (&g)[4], uint32_t w0, uint32_t w2,
+                                                               uint32_t mask, uint32_t shift, bool limited) {
+    constexpr int L = BPP - 1;   // the last dword
+    if (BPP == 4) {
+        g[0] = bgr_to_gray(d[0] & 255u, (d[0] >> 8) & 255u, (d[0] >> 16) & 255u, w0, w2);
+        g[1] = bgr_to_gray(d[L / 3] & 255u, (d[L / 3] >> 8) & 255u, (d[L / 3] >> 16) & 255u, w0, w2);
+        g[2] = bgr_to_gray(d[L - L / 3] & 255u, (d[L - L / 3] >> 8) & 255u, (d[L - L / 3] >> 16) & 255u, w0, w2);
+        g[3] = bgr_to_gray(d[L] & 255u, (d[L] >> 8) & 255u, (d[L] >> 16) & 255u, w0, w2);
+    } else if (BPP == 3) {
+        g[0] = bgr_to_gray(d[0] & 255u, (d[0] >> 8) & 255u, (d[0] >> 16) & 255u, w0, w2);
+        g[1] = bgr_to_gray(d[0] >> 24, d[L / 2] & 255u, (d[L / 2] >> 8) & 255u, w0, w2);
+        g[2] = bgr_to_gray((d[L / 2] >> 16) & 255u, d[L / 2] >> 24, d[L] & 255u, w0, w2);
+        g[3] = bgr_to_gray((d[L] >> 8) & 255u, (d[L] >> 16) & 255u, d[L] >> 24, w0, w2);
+    } else if (BPP == 2) {
+        g[0] = narrow_to_gray(d[0], mask, shift, limited);
+        g[1] = narrow_to_gray(d[0] >> 16, mask, shift, limited);
+        g[2] = narrow_to_gray(d[L], mask, shift, limited);
+        g[3] = narrow_to_gray(d[L] >> 16, mask, shift, limited);
+    } else {
+        g[0] = narrow_to_gray(d[0], mask, 0u, limited);
+        g[1] = narrow_to_gray(d[0] >> 8, mask, 0u, limited);
+        g[2] = narrow_to_gray(d[0] >> 16, mask, 0u, limited);
+        g[3] = narrow_to_gray(d[0] >> 24, mask, 0u, limited);
+    }
+}
+// A source pixel that starts `s` units after the first of N plane pixels (cw units each) and is w <= cw units wide: its gray value,
+// weighted by the overlap, to the (at most two) plane pixels it overlaps
+template <int N> __device__ __forceinline__ void scale_add(uint32_t (&r)[N], int s, int w, int cw, uint32_t g) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const int ov = min(s + w, (k + 1) * cw) - max(s, k * cw);
+        if (ov > 0) r[k] += (uint32_t)ov * g;
+    }
+}
+// N consecutive pixels of plane row y from column x on: their values.  The N footprints are one run of source columns in each
+// footprint row: the lane walks the run four source pixels at a time through load_dwords_unaligned -- all 4 * BPP bytes of such a
+// step are bytes of the crop's row, so every fetched dword holds a needed byte -- and the run's last 1..3 pixels byte by byte.
+template <int BPP, int N> __device__ __forceinline__ void d_scale_pixels(const ScaleArgs &a, uint32_t x, uint32_t y, uint32_t (&out)[N]) {
+    const int w = a.w, h = a.h, cw = a.cw, ch = a.ch;
+    const bool rgb = (a.fmt & UPF_RGB) != 0, limited = (a.fmt & UPF_LIMITED) != 0, wide = a.wide != 0;
+    const uint32_t w0 = rgb ? 4899u : 1868u, w2 = rgb ? 1868u : 4899u;
+    const uint32_t mask = (BPP == 1 || (a.fmt & UPF_LOW_BYTE)) ? 0xffu : 0xffffu, shift = BPP == 2 ? (uint32_t)(a.fmt & UPF_SHIFT) : 0u;
+    uint32_t j0, ry, i0, rx;
+    scale_muldiv(y, (uint32_t)ch, (uint32_t)h, wide, j0, ry);   // source row j0 starts ry units above the plane row (a source row: h units)
+    scale_muldiv(x, (uint32_t)cw, (uint32_t)w, wide, i0, rx);   // source column i0 starts rx units left of plane pixel x
+    const int end = N * cw;
+    uint32_t acc[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) acc[k] = 0;
+    const uint8_t *row0 = a.src + (size_t)j0 * (size_t)a.sstride + (size_t)i0 * BPP;
+    for (int t = -(int)ry; t < ch; t += h, row0 += a.sstride) {
+        const uint32_t b = (uint32_t)(min(t + h, ch) - max(t, 0));
+        uint32_t r[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) r[k] = 0;
+        const uint8_t *p = row0;
+        int s = -(int)rx;
+        for (; s + 3 * w < end; s += 4 * w, p += 4 * BPP) {   // the fourth pixel of the step starts inside the run
+            uint32_t d[BPP + 1], g[4];
+            load_dwords_unaligned<BPP>(reinterpret_cast<uintptr_t>(p), d);
+            scale_gray4<BPP>(d, g, w0, w2, mask, shift, limited);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) scale_add<N>(r, s + q * w, w, cw, g[q]);
+        }
+        for (; s < end; s += w, p += BPP) {
+            uint32_t g;
+            if (BPP >= 3) g = bgr_to_gray(p[0], p[1], p[2], w0, w2);
+            else g = narrow_to_gray(BPP == 2 ? (uint32_t)p[0] | ((uint32_t)p[BPP - 1] << 8) : (uint32_t)p[0], mask, shift, limited);
+            scale_add<N>(r, s, w, cw, g);
+        }
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[k] += b * r[k];
+    }
+    const uint32_t area = (uint32_t)cw * (uint32_t)ch, half = area >> 1;
+#pragma unroll
+    for (int k = 0; k < N; ++k) out[k] = (acc[k] + half) / area;
+}
+// A lane owns four consecutive plane pixels = one dword store, as in d_upload_reduce; four pixels that straddle a plane row end
+// (w % 4 != 0) and the plane's last w * h % 4 pixels are computed and stored one by one.  Neighbouring lanes walk neighbouring,
+// overlapping runs of a source row: the overlap is served by the caches.
+template <int BPP> __device__ __forceinline__ void d_upload_scaled(const ScaleArgs &a) {
+    const uint32_t w = (uint32_t)a.w, total = w * (uint32_t)a.h;
+    const uint32_t n4 = (total + 3u) >> 2;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n4; i += gridDim.x * 256u) {
+        const uint32_t p0 = i << 2;
+        const uint32_t y = p0 / w, x = p0 - y * w;
+        if (x + 4u <= w) {   // (p0 + 4 <= total follows)
+            uint32_t g[4];
+            d_scale_pixels<BPP, 4>(a, x, y, g);
+            reinterpret_cast<uint32_t *>(a.dst)[i] = g[0] | (g[1] << 8) | (g[2] << 16) | (g[3] << 24);
+        } else {
+            const uint32_t pe = p0 + 4u < total ? p0 + 4u : total;
+            for (uint32_t p = p0; p < pe; ++p) {
+                const uint32_t py = p / w;
+                uint32_t g[1];
+                d_scale_pixels<BPP, 1>(a, p - py * w, py, g);
+                a.dst[p] = (uint8_t)g[0];
+            }
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_upload_scaled(ScaleArgs a) {
+    if (a.bpp == 3) return d_upload_scaled<3>(a);
+    if (a.bpp == 4) return d_upload_scaled<4>(a);
+    if (a.bpp == 2) return d_upload_scaled<2>(a);
+    d_upload_scaled<1>(a);
+}
+
 // ---------------------------------------------------------------------------------------------- tracking view (xrhip_image_render_view)
 // Line segments and discs over a frame's gray plane, all in integers.  Which primitive a pixel shows must not depend on how the GPU
 // schedules the lanes: k_view_stamp takes atomicMax of a word ordered like the priority rule into a 32-bit owner plane (cleared per

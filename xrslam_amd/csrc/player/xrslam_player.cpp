@@ -7,9 +7,11 @@
 //
 //   xrslam-player --slam configs/euroc_slam.yaml --device configs/euroc_sensor.yaml --euroc <dir>/mav0
 //                 [--out traj.tum] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined]
-//                 [--push-color] [--push-format gray16|rgb|rgba]
+//                 [--push-color] [--push-format gray16|rgb|rgba] [--push-scaled]
 //
 // (--push-color: a colour PNG is pushed as BGR / BGRA with channel 3 / 4 and reduced to gray by the library instead of by the reader.)
+// (--push-scaled: a PNG larger than cam0.resolution is pushed at its own size, the whole frame as the crop, and cropped / area-scaled
+// down by the library -- through any --push-color / --push-format setting; without the flag a size mismatch is an error.)
 // (--push-format: a 16-bit PNG is handed to the library as GRAY16 instead of being stripped to its high byte by the reader; a colour
 // PNG as RGB8 / RGBA8 -- XRSLAMAmdPushImageFormat.)
 // (--pipelined: XRSLAMAmdSetThreading(1), the reference's XRSLAM_ENABLE_THREADING build with deterministic hand-offs.)
@@ -56,7 +58,7 @@ static const TruthRow *nearest_truth(const std::vector<TruthRow> &gt, double t, 
 
 int main(int argc, char **argv) {
     std::map<std::string, std::string> opt;
-    bool undistort = true, host_undistort = false, pipelined = false, push_color = false;
+    bool undistort = true, host_undistort = false, pipelined = false, push_color = false, push_scaled = false;
     int png_keep = PNG_GRAY;   // --push-format
     // the reference's option names (main.cpp:57-71) map onto ours
     const std::map<std::string, std::string> alias = {{"-sc", "slam"}, {"--slamconfig", "slam"}, {"-dc", "device"},
@@ -68,6 +70,7 @@ int main(int argc, char **argv) {
         else if (a == "--host-undistort") host_undistort = true;   // the reference's arrangement: the reader rectifies on the host
         else if (a == "--pipelined") pipelined = true;
         else if (a == "--push-color") push_color = true;   // colour PNGs are pushed as BGR / BGRA (channel 3 / 4): the library reduces them
+        else if (a == "--push-scaled") push_scaled = true;   // PNGs larger than cam0.resolution are scaled down by the library
         else if (a == "--push-format" && i + 1 < argc) {
             const std::string f = argv[++i];
             if (f == "gray16") png_keep = PNG_KEEP_GRAY16;
@@ -99,7 +102,7 @@ int main(int argc, char **argv) {
     }
     if (!opt.count("slam") || !opt.count("device") || !opt.count("euroc")) {
         std::fprintf(stderr, "usage: xrslam-player --slam cfg.yaml --device sensor.yaml --euroc <dir>/mav0 [--out traj.tum] "
-                             "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color] [--push-format gray16|rgb|rgba]\n"
+                             "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color] [--push-format gray16|rgb|rgba] [--push-scaled]\n"
                              "       [--view-out DIR [--view-every N] [--view-mode reference|age] [--view-trail K]]\n"
                              "   or: xrslam-player -sc cfg.yaml -dc sensor.yaml [--tum traj.tum] [--csv traj.csv] [-p] "
                              "euroc://<dir>/mav0 | tum://<dir>/mav0\n");
@@ -223,12 +226,26 @@ int main(int argc, char **argv) {
             }
             // the library copies cam0.resolution rows x columns out of the buffer it is handed
             // (XRSLAMManager.cpp:113-131 does the same with the configured size): a frame of any other size is an error
-            if (img.w != (int)cfg.cam_resolution[0] || img.h != (int)cfg.cam_resolution[1]) {
+            const bool oversized = push_scaled && img.w >= (int)cfg.cam_resolution[0] && img.h >= (int)cfg.cam_resolution[1] &&
+                                   (img.w != (int)cfg.cam_resolution[0] || img.h != (int)cfg.cam_resolution[1]);
+            if (oversized) {   // --push-scaled: the frame goes in at its own size, the whole of it as the crop
+                if (undistort && cfg.cam_distortion_flag && !device_undistort) {
+                    std::fprintf(stderr, "%s: --push-scaled with --host-undistort: the reader rectifies working-size frames only\n",
+                                 cam[ev.index].filename.c_str());
+                    break;
+                }
+                io_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - io0).count();
+                const XRSLAMAmdFrameFormat ff{img.pixel_format >= 0 ? img.pixel_format
+                                              : img.channels == 3 ? (int)XRSLAM_AMD_PIXEL_BGR8
+                                              : img.channels == 4 ? (int)XRSLAM_AMD_PIXEL_BGRA8 : (int)XRSLAM_AMD_PIXEL_GRAY8, 0, 0};
+                const XRSLAMAmdFrameGeometry geo{img.w, img.h, 0, 0, img.w, img.h};
+                XRSLAMAmdPushImageScaled(img.px.data(), img.w * img.channels, &ff, &geo, 0, ev.t);
+            } else if (img.w != (int)cfg.cam_resolution[0] || img.h != (int)cfg.cam_resolution[1]) {
                 std::fprintf(stderr, "%s: image is %dx%d, the device configuration says %dx%d\n", cam[ev.index].filename.c_str(), img.w,
                              img.h, (int)cfg.cam_resolution[0], (int)cfg.cam_resolution[1]);
                 break;
             }
-            const bool rectify_here = undistort && cfg.cam_distortion_flag && !device_undistort;
+            const bool rectify_here = !oversized && undistort && cfg.cam_distortion_flag && !device_undistort;
             if (img.channels != 1 && rectify_here) {   // the host remap takes gray: reduced first, rectified second, as in the library
                 std::vector<uint8_t> g((size_t)img.w * img.h);
                 for (size_t i = 0; i < g.size(); ++i) {
@@ -251,8 +268,10 @@ int main(int argc, char **argv) {
                 und->apply(img.px.data(), img.w, rectified.data(), img.w);
                 pixels = rectified.data();
             }
-            io_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - io0).count();
-            if (img.pixel_format >= 0) {
+            if (!oversized) io_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - io0).count();
+            if (oversized) {
+                // (pushed above)
+            } else if (img.pixel_format >= 0) {
                 const XRSLAMAmdFrameFormat ff{img.pixel_format, 0, 0};
                 XRSLAMAmdPushImageFormat(pixels, img.w * img.channels, &ff, 0, ev.t);
             } else {

@@ -76,6 +76,16 @@ def frame_format(pixel_format):
     return XRSLAMAmdFrameFormat(PIXEL_FORMATS[f[0]] if isinstance(f[0], str) else int(f[0]), int(f[1]), int(f[2]))
 
 
+class XRSLAMAmdFrameGeometry(C.Structure):
+    _fields_ = [("src_width", C.c_int), ("src_height", C.c_int), ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int),
+                ("crop_height", C.c_int)]
+
+
+def frame_geometry(geo):
+    """(src_width, src_height, crop_x, crop_y, crop_width, crop_height) -> XRSLAMAmdFrameGeometry"""
+    return geo if isinstance(geo, XRSLAMAmdFrameGeometry) else XRSLAMAmdFrameGeometry(*[int(v) for v in geo])
+
+
 class XRSLAMAmdInitReport(C.Structure):
     _fields_ = [("attempts", C.c_long), ("successes", C.c_long), ("sfm_candidate", C.c_int),
                 ("sfm_triangulated", C.c_int), ("scale", C.c_double), ("gravity", C.c_double * 3),
@@ -107,6 +117,13 @@ def load(lib_path):
     if have_format:
         lib.XRSLAMAmdPushImageFormat.argtypes = [C.c_void_p, C.c_int, C.POINTER(XRSLAMAmdFrameFormat), C.c_int, C.c_double]
         lib.XRSLAMAmdPushImageFormat.restype = None
+    have_scaled = hasattr(lib, "XRSLAMAmdPushImageScaled")
+    if have_scaled:
+        lib.XRSLAMAmdPushImageScaled.argtypes = [C.c_void_p, C.c_int, C.POINTER(XRSLAMAmdFrameFormat), C.POINTER(XRSLAMAmdFrameGeometry),
+                                                 C.c_int, C.c_double]
+        lib.XRSLAMAmdPushImageScaled.restype = None
+        lib.XRSLAMAmdScaleIntrinsics.argtypes = [C.c_void_p, C.POINTER(XRSLAMAmdFrameGeometry), C.c_int, C.c_int, C.c_void_p]
+        lib.XRSLAMAmdScaleIntrinsics.restype = None
     lib.XRSLAMAmdGetTimes.argtypes = [C.POINTER(XRSLAMAmdTimes)]
     lib.XRSLAMAmdGetTimes.restype = None
     lib.XRSLAMAmdLastError.restype = C.c_char_p
@@ -166,6 +183,14 @@ def load(lib_path):
                                                           C.POINTER(XRSLAMAmdFrameFormat), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                           C.c_int, C.c_void_p]
             lib.XRSLAMAmdInstanceReplayFormat.restype = C.c_int
+        if have_scaled:
+            lib.XRSLAMAmdInstancePushImageScaled.argtypes = [H, C.c_void_p, C.c_int, C.POINTER(XRSLAMAmdFrameFormat),
+                                                             C.POINTER(XRSLAMAmdFrameGeometry), C.c_int, C.c_double]
+            lib.XRSLAMAmdInstancePushImageScaled.restype = None
+            lib.XRSLAMAmdInstanceReplayScaled.argtypes = [H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int,
+                                                          C.POINTER(XRSLAMAmdFrameFormat), C.POINTER(XRSLAMAmdFrameGeometry), C.c_int,
+                                                          C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p]
+            lib.XRSLAMAmdInstanceReplayScaled.restype = C.c_int
     if hasattr(lib, "XRSLAMAmdGroupCreate"):
         lib.XRSLAMAmdGroupCreate.argtypes = [C.POINTER(C.c_void_p)]
         lib.XRSLAMAmdGroupDestroy.argtypes = [C.c_void_p]
@@ -228,6 +253,8 @@ class _Api:
             names["push_image_device_color"] = ("XRSLAMAmdPushImageDeviceColor", "XRSLAMAmdInstancePushImageDeviceColor")
         if hasattr(lib, "XRSLAMAmdPushImageFormat"):
             names["push_image_format"] = ("XRSLAMAmdPushImageFormat", "XRSLAMAmdInstancePushImageFormat")
+        if hasattr(lib, "XRSLAMAmdPushImageScaled"):
+            names["push_image_scaled"] = ("XRSLAMAmdPushImageScaled", "XRSLAMAmdInstancePushImageScaled")
         if hasattr(lib, "XRSLAMAmdRenderTrackingView"):
             names["get_features"] = ("XRSLAMAmdGetFeatures", "XRSLAMAmdInstanceGetFeatures")
             names["set_feature_history"] = ("XRSLAMAmdSetFeatureHistory", "XRSLAMAmdInstanceSetFeatureHistory")
@@ -241,13 +268,17 @@ class Session:
     instance=True -- an XRSLAMAmdInstance of its own, so that several sessions can live in one process.
     channels 3 / 4: seq["frames"] (or device_frames) hold interleaved BGR / BGRA frames, [n][h][w][channels].
     pixel_format (see frame_format): the frames are rows of bytes in that layout, [n][h][row bytes] (or [n][h][w][bytes per pixel]),
-    pushed through XRSLAMAmdPushImageFormat / XRSLAMAmdInstanceReplayFormat from host memory or from device_frames."""
+    pushed through XRSLAMAmdPushImageFormat / XRSLAMAmdInstanceReplayFormat from host memory or from device_frames.
+    geometry (see frame_geometry): the frames are larger than cam0.resolution and go through XRSLAMAmdPushImageScaled /
+    XRSLAMAmdInstanceReplayScaled, in pixel_format (None: GRAY8)."""
 
     def __init__(self, lib_path, seq, slam_yaml=SLAM_YAML, sensor_yaml=SENSOR_YAML, device_frames=None,
-                 init_frames=60, instance=False, device_undistort=None, threading=0, group=None, channels=1, pixel_format=None):
+                 init_frames=60, instance=False, device_undistort=None, threading=0, group=None, channels=1, pixel_format=None,
+                 geometry=None):
         self.lib = load(lib_path)
         self.channels = int(channels)
         self.pixel_format = None if pixel_format is None else frame_format(pixel_format)
+        self.geometry = None if geometry is None else frame_geometry(geometry)
         self.seq = seq
         cfg = C.c_void_p()
         if instance:
@@ -310,14 +341,18 @@ class Session:
             return False
         t = float(self.seq["cam_t"][self.frame_k])
         self._push_imu_until(t)
-        if self.pixel_format is not None:
+        if self.pixel_format is not None or self.geometry is not None:
             if self.device_frames is not None:
                 base, fbytes, stride = self.device_frames
                 ptr, on_dev = C.c_void_p(base + self.frame_k * fbytes), 1
             else:
                 fr = self.seq["frames"][self.frame_k]
                 ptr, stride, on_dev = C.c_void_p(fr.ctypes.data), fr.strides[0], 0
-            self.api.push_image_format(ptr, stride, C.byref(self.pixel_format), on_dev, t)
+            if self.geometry is not None:
+                self.api.push_image_scaled(ptr, stride, None if self.pixel_format is None else C.byref(self.pixel_format),
+                                           C.byref(self.geometry), on_dev, t)
+            else:
+                self.api.push_image_format(ptr, stride, C.byref(self.pixel_format), on_dev, t)
         elif self.device_frames is not None:
             base, fbytes, stride = self.device_frames
             if self.channels == 1:
@@ -354,7 +389,11 @@ class Session:
             ptr, on_dev = C.c_void_p(base), 1
         else:
             ptr, fbytes, stride, on_dev = C.c_void_p(frames.ctypes.data), frames.strides[0], frames.strides[1], 0
-        if self.pixel_format is not None:
+        if self.geometry is not None:
+            k = self.lib.XRSLAMAmdInstanceReplayScaled(self._handle, imu.ctypes.data, len(imu), cam_t.ctypes.data, len(cam_t), ptr,
+                                                       fbytes, stride, None if self.pixel_format is None else C.byref(self.pixel_format),
+                                                       C.byref(self.geometry), on_dev, C.byref(ic), C.byref(fc), int(n), out.ctypes.data)
+        elif self.pixel_format is not None:
             k = self.lib.XRSLAMAmdInstanceReplayFormat(self._handle, imu.ctypes.data, len(imu), cam_t.ctypes.data, len(cam_t), ptr,
                                                        fbytes, stride, C.byref(self.pixel_format), on_dev, C.byref(ic), C.byref(fc),
                                                        int(n), out.ctypes.data)

@@ -7,6 +7,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
+from .abi import FrameGeometry
 
 
 class KltStats(C.Structure):
@@ -48,6 +49,9 @@ def _bind():
     L.xrhip_image_upload_color_distorted.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.xrhip_image_upload_format.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.xrhip_image_upload_format_distorted.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.xrhip_image_upload_scaled.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FrameGeometry)]
+    L.xrhip_image_upload_scaled_distorted.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FrameGeometry)]
+    L.xrhip_debug_stream_span.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
     L.xrhip_debug_get_raw.argtypes = [vp, vp]
     L.xrhip_debug_set_fused_pyramid.argtypes = [vp, C.c_int]
     L.xrhip_debug_get_level_padded.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -105,6 +109,12 @@ class KltContext:
         ms, n = C.c_double(0), C.c_longlong(0)
         check(L().xrhip_debug_view_timing(self._h, int(enable), C.byref(ms), C.byref(n), 1 if reset else 0))
         return ms.value, n.value
+
+    def stream_span(self, phase):
+        """HIP-event time of what the context issues between stream_span(0) and stream_span(1); the latter returns it in ms."""
+        ms = C.c_double(0)
+        check(L().xrhip_debug_stream_span(self._h, int(phase), C.byref(ms)))
+        return ms.value
 
     def set_fused_pyramid(self, on):
         """Development / parity switch: preprocess() builds the pyramid in one launch (default) or in the five it replaces."""
@@ -203,6 +213,28 @@ class HipImage:
         """upload_format for a frame as the camera recorded it: reduced to gray, then rectified (KltContext.set_undistort_map)."""
         ptr, stride = self._format_args(pixels, on_device, stride)
         check(L().xrhip_image_upload_format_distorted(self._h, ptr, stride, int(fmt), int(bits), int(limited_range), 1 if on_device else 0))
+
+    def _scaled_args(self, pixels, geo, on_device, stride):
+        g = geo if isinstance(geo, FrameGeometry) else FrameGeometry(*[int(v) for v in geo])
+        if on_device:   # pixels: a device pointer (int) to row 0 of the source frame
+            return C.c_void_p(int(pixels)), int(stride), g
+        assert pixels.dtype == np.uint8 and pixels.ndim in (2, 3) and pixels.shape[0] == g.src_height, pixels.shape
+        assert pixels.strides[-1] == 1 and (pixels.ndim == 2 or pixels.strides[1] == pixels.shape[2]), pixels.strides
+        return _p(pixels), pixels.strides[0], g
+
+    def upload_scaled(self, pixels, geo, fmt=0, bits=0, limited_range=0, on_device=False, stride=None):
+        """A frame larger than the context's plane, in any XRHIP_PIXFMT_* layout: the crop of `geo` = (src_width, src_height, crop_x,
+        crop_y, crop_width, crop_height) is area-averaged down to the plane on its way in.  `pixels`: a uint8 array of the source
+        frame's bytes, [src_height][row bytes] or [src_height][src_width][bytes per pixel] (rows may be strided), or -- on_device -- a
+        device pointer to row 0 of the source frame with its row stride in bytes."""
+        ptr, stride, g = self._scaled_args(pixels, geo, on_device, stride)
+        check(L().xrhip_image_upload_scaled(self._h, ptr, stride, int(fmt), int(bits), int(limited_range), 1 if on_device else 0, C.byref(g)))
+
+    def upload_scaled_distorted(self, pixels, geo, fmt=0, bits=0, limited_range=0, on_device=False, stride=None):
+        """upload_scaled for a frame as the camera recorded it: scaled, then rectified (KltContext.set_undistort_map)."""
+        ptr, stride, g = self._scaled_args(pixels, geo, on_device, stride)
+        check(L().xrhip_image_upload_scaled_distorted(self._h, ptr, stride, int(fmt), int(bits), int(limited_range), 1 if on_device else 0,
+                                                      C.byref(g)))
 
     def raw(self):
         """The 8-bit frame preprocess() will read (parity aid)."""
