@@ -18,9 +18,12 @@ extern "C" int fh_feature_track(const uint8_t *a, const uint8_t *b, int w, const
                                                   (int)cfg.feature_tracker_clahe_height),
                            "xrhip_image_preprocess");
         };
+        xrh::FrameInput in;   // (8-bit gray, dense rows, host memory)
+        in.stride = w;
         auto f1 = std::make_unique<xrh::Frame>();
         f1->K = cfg.K;
-        f1->image = P.make_image(a, w, 0.0, false);
+        in.pixels = a;
+        f1->image = P.make_image(in, 0.0);
         pre(f1.get());
         xrh::frame_detect_keypoints(P, f1.get());
         out3[0] = (int)f1->keypoint_num();
@@ -28,7 +31,8 @@ extern "C" int fh_feature_track(const uint8_t *a, const uint8_t *b, int w, const
         xrh::Frame *last = map->get_frame(0);
         auto f2 = std::make_unique<xrh::Frame>();
         f2->K = cfg.K;
-        f2->image = P.make_image(b, w, 0.05, false);
+        in.pixels = b;
+        f2->image = P.make_image(in, 0.05);
         pre(f2.get());
         xrh::frame_track_keypoints(P, last, f2.get());
         out3[1] = f2->tag(xrh::FT_NO_TRANSLATION) ? 1 : 0;

@@ -274,3 +274,48 @@ def test_plain_and_scaled_frames_alternate_through_the_same_context(klt, hbm):
         im.upload(g[::-1].copy())
         np.testing.assert_array_equal(im.raw(), g[::-1])
     ctx.synchronize()
+
+
+def test_a_group_member_uploads_through_every_entry_point_without_waiting(klt):
+    """A context joined to an instance group defers its uploads and never waits between them: five host frames, one per image and
+    each through another entry point, more of them than there are pinned slots, the fourth a crop larger than anything staged before
+    (the slots and the scaled upload's scratch grow while earlier uploads are in flight).  Only then are the planes read: every one
+    is its model, bit for bit -- and again in a second round, with every buffer at its final size."""
+    from xrslam_amd import _lib
+    lib = _lib.lib()
+    lib.xrhip_group_create.argtypes = [C.POINTER(C.c_void_p)]
+    lib.xrhip_group_destroy.argtypes = [C.c_void_p]
+    lib.xrhip_klt_join_group.argtypes = [C.c_void_p, C.c_void_p]
+    W, H = 97, 66
+    geo = (2 * W + 6, 2 * H + 4, 3, 1, 2 * W + 1, 2 * H + 1)
+    assert geo[4] * geo[5] * 3 > W * H * 4
+    ctx = klt.KltContext(W, H, 50)
+    ims = [ctx.image() for _ in range(5)]
+    group = C.c_void_p()
+    assert lib.xrhip_group_create(C.byref(group)) == 0
+    assert lib.xrhip_klt_join_group(ctx._h, group) == 0, lib.xrhip_last_error()
+    try:
+        for rnd in range(2):
+            g0, g1 = noise_image(W, H, seed=11 + rnd), noise_image(W, H, seed=21 + rnd)
+            bgra = cf.random_pixels(W, H, 4, seed=31 + rnd)
+            odd = np.zeros(1 + H * W * 2, np.uint8)
+            yuyv = odd[1:].reshape(H, W, 2)                                   # (its first byte lies at an odd address)
+            yuyv[...] = cf.random_pixels(W, H, 2, seed=41 + rnd)
+            assert yuyv.ctypes.data % 2 == 1
+            _, big = frame(cf.random_pixels(geo[0], geo[1], 3, seed=51 + rnd), 5)
+            ims[0].upload(g0)
+            ims[1].upload_color(bgra)
+            ims[2].upload_format(yuyv, pm.YUYV)
+            ims[3].upload_scaled(big, geo, pm.RGB8)
+            ims[4].upload(g1)
+            want = [g0, pm.reduce(bgra, pm.BGRA8), pm.reduce(yuyv, pm.YUYV), sm.scale(big, geo, W, H, pm.RGB8), g1]
+            for k, (im, w) in enumerate(zip(ims, want)):
+                np.testing.assert_array_equal(im.raw(), w, err_msg="round %d, image %d" % (rnd, k))
+        ctx.synchronize()
+    finally:
+        for im in ims:
+            im.close()
+        lib.xrhip_klt_join_group(ctx._h, None)
+        ctx.close()
+        lib.xrhip_group_destroy(group)
+

@@ -68,6 +68,19 @@ inline bool have_format_upload() { return xrhip_image_upload_format != nullptr &
 inline bool have_scaled_upload() { return xrhip_image_upload_scaled != nullptr && xrhip_image_upload_scaled_distorted != nullptr; }
 inline bool have_color_upload() { return xrhip_image_upload_color != nullptr && xrhip_image_upload_color_distorted != nullptr; }
 
+// A camera frame as it is handed to Pipeline::make_image, from host memory or HBM
+struct FrameInput {
+    const uint8_t *pixels = nullptr;
+    int stride = 0;   // bytes
+    bool on_device = false;
+    // what a pixel is: `channels` -- 1: 8-bit gray, 3 / 4: interleaved BGR / BGRA -- or, with by_format, XRHIP_PIXFMT_* and its bits / limited_range
+    int channels = 1;
+    bool by_format = false;
+    int format = XRHIP_PIXFMT_GRAY8, bits = 0, limited_range = 0;
+    // set: the frame is larger than cam_resolution and its crop is area-averaged down to the working plane (described by format)
+    const xrhip_frame_geometry *geo = nullptr;
+};
+
 struct HipError : std::runtime_error {
     explicit HipError(const std::string &m) : std::runtime_error(m) {}
 };
@@ -311,86 +324,60 @@ struct Pipeline {
         xrhip_image_release(im);
         image_pool.push_back(im);
     }
-    // channels 1: 8-bit gray; 3 / 4: interleaved BGR / BGRA, reduced to gray by the frame's upload (xrhip_image_upload_color) -- or
-    // here, where the library behind xrslam_hip.h has no colour upload (the CPU reference build: its host arithmetic is what the
-    // device's is compared against)
-    // format other than NO_PIXEL_FORMAT (XRHIP_PIXFMT_*, with its bits / limited_range) takes the place of channels: GRAY8 without a range flag, BGR8 and
-    // BGRA8 are the frames above; every other format is reduced by xrhip_image_upload_format -- or here, with the same integer formulas
-    // (pixel_format.hpp), where the library has no such upload.
-    static constexpr int NO_PIXEL_FORMAT = INT_MIN;
+    // The frame's format is resolved and validated once; the frame then goes to the one upload of xrslam_hip.h that takes it as it is.
+    // Where the library behind that header lacks that upload (the CPU reference build has the gray ones only: its host arithmetic is what
+    // the device's is compared against), the frame is first scaled / reduced here with the same integer formulas (pixel_format.hpp).
     std::vector<uint8_t> gray_scratch;
-    std::shared_ptr<HipImage> make_image(const uint8_t *gray, int stride, double t, bool device_ptr, int channels = 1, int format = NO_PIXEL_FORMAT,
-                                         int bits = 0, int limited_range = 0, const xrhip_frame_geometry *geo = nullptr) {
+    std::shared_ptr<HipImage> make_image(const FrameInput &in, double t) {
         const int cols = (int)config.cam_resolution[0], rows = (int)config.cam_resolution[1];
         PixelFormat pf;
-        bool by_format = false;
-        // geo: the frame is larger than cam_resolution -- its crop is area-averaged down to the working plane by
-        // xrhip_image_upload_scaled (any format), or here with the same integers where the library has no such upload; what follows
-        // then sees the working-size gray frame
-        bool scaled = false;
-        int scaled_format = XRHIP_PIXFMT_GRAY8;
-        if (geo) {
-            if (format == NO_PIXEL_FORMAT) format = XRHIP_PIXFMT_GRAY8;
-            if (const char *why = describe_pixel_format(format, bits, limited_range, pf))
+        if (in.geo || in.by_format) {
+            if (const char *why = describe_pixel_format(in.format, in.bits, in.limited_range, pf))
                 throw std::runtime_error(std::string("Image format is not supported: ") + why);
-            if (!gray) throw std::runtime_error("Image geometry is not supported: null pixels");
-            if (const char *why = check_frame_geometry(geo, cols, rows, pf.bpp, stride))
+        } else {
+            if (in.channels != 1 && in.channels != 3 && in.channels != 4) throw std::runtime_error("Image channel is not supported!");
+            pf.bpp = in.channels;
+        }
+        if (in.geo) {
+            if (!in.pixels) throw std::runtime_error("Image geometry is not supported: null pixels");
+            if (const char *why = check_frame_geometry(in.geo, cols, rows, pf.bpp, in.stride))
                 throw std::runtime_error(std::string("Image geometry is not supported: ") + why);
-            if (have_scaled_upload()) {
-                scaled = true;
-            } else {
-                if (device_ptr) throw std::runtime_error("Image geometry is not supported: this library cannot scale a frame in device memory");
-                gray_scratch.resize((size_t)cols * rows);
-                scale_frame(gray_scratch.data(), cols, rows, crop_origin(gray, stride, *geo, pf.bpp), stride, geo->crop_width, geo->crop_height, pf);
-                gray = gray_scratch.data();
-                stride = cols;
-            }
-            scaled_format = format;
-            format = NO_PIXEL_FORMAT;
-            channels = 1;
+        } else if (in.by_format && (!in.pixels || (long long)in.stride < (long long)cols * pf.bpp)) {
+            throw std::runtime_error("Image format is not supported: null pixels or stride < width * bytes per pixel");
         }
-        if (format != NO_PIXEL_FORMAT) {
-            if (const char *why = describe_pixel_format(format, bits, limited_range, pf))
-                throw std::runtime_error(std::string("Image format is not supported: ") + why);
-            if (!gray || (long long)stride < (long long)cols * pf.bpp)
-                throw std::runtime_error("Image format is not supported: null pixels or stride < width * bytes per pixel");
-            by_format = pf.bpp == 2 || pf.rgb || pf.limited;
-            channels = pf.bpp;
+        // the upload that takes the frame: SCALED and FORMAT carry format / bits / limited_range, COLOR carries the channels
+        enum { GRAY, COLOR, FORMAT, SCALED } how = in.geo ? SCALED : pf.bpp == 2 || pf.rgb || pf.limited ? FORMAT : pf.bpp != 1 ? COLOR : GRAY;
+        const uint8_t *pixels = in.pixels;
+        int stride = in.stride;
+        if (how == SCALED ? !have_scaled_upload() : how == FORMAT ? !have_format_upload() : how == COLOR && !have_color_upload()) {
+            if (how == SCALED && in.on_device) throw std::runtime_error("Image geometry is not supported: this library cannot scale a frame in device memory");
+            gray_scratch.resize((size_t)cols * rows);
+            if (how == SCALED)
+                scale_frame(gray_scratch.data(), cols, rows, crop_origin(pixels, stride, *in.geo, pf.bpp), stride, in.geo->crop_width, in.geo->crop_height, pf);
+            else reduce_frame(gray_scratch.data(), pixels, stride, cols, rows, pf);   // BGR(A): cv::cvtColor BGR(A)2GRAY, (B*1868 + G*9617 + R*4899 + 8192) >> 14
+            pixels = gray_scratch.data();
+            stride = cols;
+            how = GRAY;
         }
-        if (channels != 1 && channels != 3 && channels != 4 && !by_format) throw std::runtime_error("Image channel is not supported!");
         auto img = std::make_shared<HipImage>();
         img->owner = this;
         img->h = acquire_image();
         img->t = t;
         img->w = cols;
         img->hgt = rows;
-        if (by_format ? !have_format_upload() : channels != 1 && !have_color_upload()) {
-            // BGR(A): cv::cvtColor BGR(A)2GRAY, (B*1868 + G*9617 + R*4899 + 8192) >> 14
-            if (!by_format) pf.bpp = channels;
-            gray_scratch.resize((size_t)cols * rows);
-            reduce_frame(gray_scratch.data(), gray, stride, cols, rows, pf);
-            gray = gray_scratch.data();
-            stride = cols;
-            channels = 1;
-            by_format = false;
-        }
         // a member of an instance group starts its frame together with the other members (timing only: xrslam_hip.h, frame gate)
         if (group) xrhip_klt_frame_gate(klt);
-        if (scaled) {
-            if (undistort_on_device)
-                hip_check(xrhip_image_upload_scaled_distorted(img->h, gray, stride, scaled_format, bits, limited_range, device_ptr ? 1 : 0, geo), "xrhip_image_upload_scaled_distorted");
-            else hip_check(xrhip_image_upload_scaled(img->h, gray, stride, scaled_format, bits, limited_range, device_ptr ? 1 : 0, geo), "xrhip_image_upload_scaled");
-        } else if (by_format) {
-            if (undistort_on_device)
-                hip_check(xrhip_image_upload_format_distorted(img->h, gray, stride, format, bits, limited_range, device_ptr ? 1 : 0), "xrhip_image_upload_format_distorted");
-            else hip_check(xrhip_image_upload_format(img->h, gray, stride, format, bits, limited_range, device_ptr ? 1 : 0), "xrhip_image_upload_format");
-        } else if (channels != 1) {
-            if (undistort_on_device)
-                hip_check(xrhip_image_upload_color_distorted(img->h, gray, stride, channels, device_ptr ? 1 : 0), "xrhip_image_upload_color_distorted");
-            else hip_check(xrhip_image_upload_color(img->h, gray, stride, channels, device_ptr ? 1 : 0), "xrhip_image_upload_color");
-        } else if (undistort_on_device) hip_check(xrhip_image_upload_distorted(img->h, gray, stride, device_ptr ? 1 : 0), "xrhip_image_upload_distorted");
-        else if (device_ptr) hip_check(xrhip_image_upload_device(img->h, gray, stride), "xrhip_image_upload_device");
-        else hip_check(xrhip_image_upload(img->h, gray, stride), "xrhip_image_upload");
+        const int dev = in.on_device ? 1 : 0;
+        const bool und = undistort_on_device;
+        if (how == SCALED && und) hip_check(xrhip_image_upload_scaled_distorted(img->h, pixels, stride, in.format, in.bits, in.limited_range, dev, in.geo), "xrhip_image_upload_scaled_distorted");
+        else if (how == SCALED) hip_check(xrhip_image_upload_scaled(img->h, pixels, stride, in.format, in.bits, in.limited_range, dev, in.geo), "xrhip_image_upload_scaled");
+        else if (how == FORMAT && und) hip_check(xrhip_image_upload_format_distorted(img->h, pixels, stride, in.format, in.bits, in.limited_range, dev), "xrhip_image_upload_format_distorted");
+        else if (how == FORMAT) hip_check(xrhip_image_upload_format(img->h, pixels, stride, in.format, in.bits, in.limited_range, dev), "xrhip_image_upload_format");
+        else if (how == COLOR && und) hip_check(xrhip_image_upload_color_distorted(img->h, pixels, stride, pf.bpp, dev), "xrhip_image_upload_color_distorted");
+        else if (how == COLOR) hip_check(xrhip_image_upload_color(img->h, pixels, stride, pf.bpp, dev), "xrhip_image_upload_color");
+        else if (und) hip_check(xrhip_image_upload_distorted(img->h, pixels, stride, dev), "xrhip_image_upload_distorted");
+        else if (dev) hip_check(xrhip_image_upload_device(img->h, pixels, stride), "xrhip_image_upload_device");
+        else hip_check(xrhip_image_upload(img->h, pixels, stride), "xrhip_image_upload");
         // FeatureTracker::work's first step (feature_tracker.cpp:39) depends on nothing but the frame: its launches are queued here,
         // behind the frame's DMA, so the device builds the pyramid while the host is still on its way to the tracker (input
         // synchronisation, frame construction, the interval's pre-integration launch).  Same call, same arguments.

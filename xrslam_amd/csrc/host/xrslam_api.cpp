@@ -84,26 +84,55 @@ int impl_create(Manager &m, const char *slam_config_path, const char *device_con
     return ok;
 }
 
+// A camera frame becomes the image XRSLAMRunOneFrame tracks next.  A frame that is refused does not arrive: the error is reported and
+// the pending image is dropped, so that XRSLAMRunOneFrame does not track the previous image a second time.
+// (refused: what the entry point itself found wrong with its arguments, in place of the frame)
+void push_frame(Manager &m, const xrh::FrameInput &in, double t, const char *refused = nullptr) {
+    if (!m.sys) return;
+    bind_device(m);
+    guarded(m, [&] {
+        try {
+            std::lock_guard<std::mutex> lk(m.input_mutex);
+            if (refused) throw std::runtime_error(refused);
+            m.cur_image = m.sys->P.make_image(in, t);
+        } catch (...) {
+            std::lock_guard<std::mutex> lk(m.input_mutex);
+            m.cur_image.reset();
+            throw;
+        }
+    });
+}
+xrhip_frame_geometry to_inner(const XRSLAMAmdFrameGeometry &g) {
+    return xrhip_frame_geometry{g.src_width, g.src_height, g.crop_x, g.crop_y, g.crop_width, g.crop_height};
+}
+// pixels of `channels` (fmt null) or of *fmt; geo set: larger than the working resolution
+xrh::FrameInput frame_input(const void *pixels, int stride, int on_device, int channels, const XRSLAMAmdFrameFormat *fmt,
+                            const xrhip_frame_geometry *geo = nullptr) {
+    xrh::FrameInput in;
+    in.pixels = static_cast<const uint8_t *>(pixels);
+    in.stride = stride;
+    in.on_device = on_device != 0;
+    in.channels = channels;
+    in.by_format = fmt != nullptr;
+    if (fmt) {
+        in.format = fmt->format;
+        in.bits = fmt->bits;
+        in.limited_range = fmt->limited_range;
+    }
+    in.geo = geo;
+    return in;
+}
+
 void impl_push(Manager &m, XRSLAMSensorType type, void *data) {
     if (!m.sys || !data) return;
+    if (type == XRSLAM_SENSOR_CAMERA) {   // channel 3 / 4 (BGR / BGRA): the frame's upload reduces it to gray
+        auto *im = static_cast<XRSLAMImage *>(data);
+        if (im->camera_id == 0) push_frame(m, frame_input(im->data, im->stride, 0, im->channel, nullptr), im->timeStamp);
+        return;
+    }
     bind_device(m);
     guarded(m, [&] {
         switch (type) {
-        case XRSLAM_SENSOR_CAMERA: {
-            auto *im = static_cast<XRSLAMImage *>(data);
-            if (im->camera_id != 0) break;
-            // channel 3 / 4 (BGR / BGRA): Pipeline::make_image hands the colour frame to the upload, which reduces it to gray
-            if (im->channel != 1 && im->channel != 3 && im->channel != 4) throw std::runtime_error("Image channel is not supported!");
-            try {
-                std::lock_guard<std::mutex> lk(m.input_mutex);
-                m.cur_image = m.sys->P.make_image(im->data, im->stride, im->timeStamp, false, im->channel);
-            } catch (...) {   // this frame did not arrive: XRSLAMRunOneFrame must not track the previous image a second time
-                std::lock_guard<std::mutex> lk(m.input_mutex);
-                m.cur_image.reset();
-                throw;
-            }
-            break;
-        }
         case XRSLAM_SENSOR_ACCELERATION: {
             auto *a = static_cast<XRSLAMAcceleration *>(data);
             m.sys->track_accelerometer(a->timestamp, a->data[0], a->data[1], a->data[2], false);
@@ -233,61 +262,22 @@ void impl_set_initial_state(Manager &m, double t, const double q[4], const doubl
 }
 
 void impl_push_image_device(Manager &m, const void *gray_dev, int stride, double timestamp, int channels = 1) {
-    if (!m.sys) return;
-    bind_device(m);
-    guarded(m, [&] {
-        try {
-            std::lock_guard<std::mutex> lk(m.input_mutex);
-            if (channels != 1 && channels != 3 && channels != 4) throw std::runtime_error("Image channel is not supported!");
-            m.cur_image = m.sys->P.make_image(static_cast<const uint8_t *>(gray_dev), stride, timestamp, true, channels);
-        } catch (...) {
-            std::lock_guard<std::mutex> lk(m.input_mutex);
-            m.cur_image.reset();
-            throw;
-        }
-    });
+    push_frame(m, frame_input(gray_dev, stride, 1, channels, nullptr), timestamp);
 }
 
 // A frame in one of the XRSLAMAmdPixelFormat layouts, from host memory or HBM.  A bad format drops the frame and sets the last error.
 void impl_push_image_format(Manager &m, const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt, int on_device, double timestamp) {
-    if (!m.sys) return;
-    bind_device(m);
-    guarded(m, [&] {
-        try {
-            std::lock_guard<std::mutex> lk(m.input_mutex);
-            if (!fmt || !pixels) throw std::runtime_error("Image format is not supported: null pixels or format");
-            m.cur_image = m.sys->P.make_image(static_cast<const uint8_t *>(pixels), stride, timestamp, on_device != 0, 1, fmt->format, fmt->bits,
-                                              fmt->limited_range);
-        } catch (...) {
-            std::lock_guard<std::mutex> lk(m.input_mutex);
-            m.cur_image.reset();
-            throw;
-        }
-    });
+    push_frame(m, frame_input(pixels, stride, on_device, 1, fmt), timestamp,
+               fmt && pixels ? nullptr : "Image format is not supported: null pixels or format");
 }
 
 // A frame larger than the working resolution (XRSLAMAmdFrameGeometry), of any format (null: GRAY8).  A bad geometry or format drops
 // the frame and sets the last error.
-xrhip_frame_geometry to_inner(const XRSLAMAmdFrameGeometry &g) {
-    return xrhip_frame_geometry{g.src_width, g.src_height, g.crop_x, g.crop_y, g.crop_width, g.crop_height};
-}
 void impl_push_image_scaled(Manager &m, const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt, const XRSLAMAmdFrameGeometry *geo,
                             int on_device, double timestamp) {
-    if (!m.sys) return;
-    bind_device(m);
-    guarded(m, [&] {
-        try {
-            std::lock_guard<std::mutex> lk(m.input_mutex);
-            if (!geo || !pixels) throw std::runtime_error("Image geometry is not supported: null pixels or geometry");
-            const xrhip_frame_geometry g = to_inner(*geo);
-            m.cur_image = m.sys->P.make_image(static_cast<const uint8_t *>(pixels), stride, timestamp, on_device != 0, 1,
-                                              fmt ? fmt->format : (int)XRSLAM_AMD_PIXEL_GRAY8, fmt ? fmt->bits : 0, fmt ? fmt->limited_range : 0, &g);
-        } catch (...) {
-            std::lock_guard<std::mutex> lk(m.input_mutex);
-            m.cur_image.reset();
-            throw;
-        }
-    });
+    const xrhip_frame_geometry g = geo ? to_inner(*geo) : xrhip_frame_geometry{};
+    push_frame(m, frame_input(pixels, stride, on_device, 1, fmt, &g), timestamp,
+               geo && pixels ? nullptr : "Image geometry is not supported: null pixels or geometry");
 }
 
 void impl_get_camera_config(Manager &m, XRSLAMAmdCameraConfig *out) {
@@ -664,10 +654,9 @@ void XRSLAMAmdGroupGetStats(XRSLAMAmdGroup *grp, void *out, int reset) {
 // The player's loop (xrslam-pc/player/src/main.cpp:116-169) for n_steps camera frames of a pre-staged sequence, without a
 // host-language round trip per sensor sample: at equal timestamps gyroscope, then accelerometer, then camera
 // (IO/async_dataset_reader.cpp:41-48); RunOneFrame and the state / pose query after every image.
-// (fmt: the frames' XRSLAMAmdFrameFormat, or null for `channels`; geo: frames larger than the working resolution)
+// (frame: what every frame is -- stride, format, geometry, host or HBM; its pixels are frames + k * frame_bytes)
 static int replay(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames, const void *frames,
-                  size_t frame_bytes, int stride, int channels, const XRSLAMAmdFrameFormat *fmt, int on_device, int *imu_cursor,
-                  int *frame_cursor, int n_steps, double *poses_out8, const XRSLAMAmdFrameGeometry *geo = nullptr) {
+                  size_t frame_bytes, xrh::FrameInput frame, int *imu_cursor, int *frame_cursor, int n_steps, double *poses_out8) {
     if (!inst || !imu7 || !cam_t || !frames || !imu_cursor || !frame_cursor) return -1;
     Manager &m = inst->m;
     int n_poses = 0;
@@ -693,23 +682,8 @@ static int replay(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const 
             ++k;
         }
         *imu_cursor = k;
-        const unsigned char *img = static_cast<const unsigned char *>(frames) + (size_t)fk * frame_bytes;
-        if (geo) {
-            impl_push_image_scaled(m, img, stride, fmt, geo, on_device, t);
-        } else if (fmt) {
-            impl_push_image_format(m, img, stride, fmt, on_device, t);
-        } else if (on_device) {
-            impl_push_image_device(m, img, stride, t, channels);
-        } else {
-            XRSLAMImage im;
-            im.data = const_cast<unsigned char *>(img);
-            im.timeStamp = t;
-            im.stride = stride;
-            im.camera_id = 0;
-            im.channel = channels;
-            im.ext = nullptr;
-            impl_push(m, XRSLAM_SENSOR_CAMERA, &im);
-        }
+        frame.pixels = static_cast<const uint8_t *>(frames) + (size_t)fk * frame_bytes;
+        push_frame(m, frame, t);
         impl_run(m);
         XRSLAMState state = XRSLAM_STATE_INITIALIZING;
         impl_get_result(m, XRSLAM_RESULT_STATE, &state);
@@ -729,16 +703,16 @@ static int replay(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const 
 int XRSLAMAmdInstanceReplayColor(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
                                  const void *frames, size_t frame_bytes, int stride, int channels, int on_device,
                                  int *imu_cursor, int *frame_cursor, int n_steps, double *poses_out8) {
-    return replay(inst, imu7, n_imu, cam_t, n_frames, frames, frame_bytes, stride, channels, nullptr, on_device, imu_cursor, frame_cursor,
-                  n_steps, poses_out8);
+    return replay(inst, imu7, n_imu, cam_t, n_frames, frames, frame_bytes, frame_input(nullptr, stride, on_device, channels, nullptr), imu_cursor,
+                  frame_cursor, n_steps, poses_out8);
 }
 
 int XRSLAMAmdInstanceReplayFormat(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
                                   const void *frames, size_t frame_bytes, int stride, const XRSLAMAmdFrameFormat *fmt, int on_device,
                                   int *imu_cursor, int *frame_cursor, int n_steps, double *poses_out8) {
     if (!fmt) return -1;
-    return replay(inst, imu7, n_imu, cam_t, n_frames, frames, frame_bytes, stride, 1, fmt, on_device, imu_cursor, frame_cursor, n_steps,
-                  poses_out8);
+    return replay(inst, imu7, n_imu, cam_t, n_frames, frames, frame_bytes, frame_input(nullptr, stride, on_device, 1, fmt), imu_cursor,
+                  frame_cursor, n_steps, poses_out8);
 }
 
 int XRSLAMAmdInstanceReplayScaled(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,
@@ -746,8 +720,9 @@ int XRSLAMAmdInstanceReplayScaled(XRSLAMAmdInstance *inst, const double *imu7, i
                                   const XRSLAMAmdFrameGeometry *geo, int on_device, int *imu_cursor, int *frame_cursor, int n_steps,
                                   double *poses_out8) {
     if (!geo) return -1;
-    return replay(inst, imu7, n_imu, cam_t, n_frames, frames, frame_bytes, stride, 1, fmt, on_device, imu_cursor, frame_cursor, n_steps,
-                  poses_out8, geo);
+    const xrhip_frame_geometry g = to_inner(*geo);
+    return replay(inst, imu7, n_imu, cam_t, n_frames, frames, frame_bytes, frame_input(nullptr, stride, on_device, 1, fmt, &g), imu_cursor,
+                  frame_cursor, n_steps, poses_out8);
 }
 
 int XRSLAMAmdInstanceReplay(XRSLAMAmdInstance *inst, const double *imu7, int n_imu, const double *cam_t, int n_frames,

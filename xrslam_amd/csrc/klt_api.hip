@@ -646,19 +646,61 @@ static void copy_to_pinned(uint8_t *dst, const uint8_t *src, size_t n) {
     std::memcpy(dst, src, n);
 }
 
-// The pinned slots hold a gray frame until the first colour frame arrives: a gray-only caller never pays for the colour size.
+// ------------------------------------------------------------------------------------------------------------ frames on their way in
+// What an upload entry point was handed.  Every xrhip_image_upload* builds one and calls upload_frame: the frame is validated once,
+// goes one way into the plane (im->raw, or undist_src when the undistortion remap follows) and the image's state is reset in one place.
+struct FrameSource {
+    const uint8_t *pixels;
+    int stride;
+    xrh::PixelFormat pf;   // (default: 8-bit gray)
+    bool on_device;        // pixels lie in HBM and are read where they lie
+    const xrhip_frame_geometry *geo;
+    bool scaled;           // larger than the plane: the crop of `geo` is area-averaged down (geo == nullptr is then an error)
+};
+static FrameSource frame_source(const void *pixels, int stride, int on_device, const xrhip_frame_geometry *geo = nullptr, bool scaled = false) {
+    return FrameSource{static_cast<const uint8_t *>(pixels), stride, xrh::PixelFormat(), on_device != 0, geo, scaled};
+}
+// the older entry points' `channels`: 1 GRAY8, 3 BGR8, 4 BGRA8 (nullptr, or what is wrong: as describe_pixel_format)
+static const char *describe_channels(int channels, xrh::PixelFormat &pf) {
+    if (channels != 1 && channels != 3 && channels != 4) return "channels must be 1, 3 (BGR) or 4 (BGRA)";
+    return xrh::describe_pixel_format(channels == 1 ? XRHIP_PIXFMT_GRAY8 : channels == 3 ? XRHIP_PIXFMT_BGR8 : XRHIP_PIXFMT_BGRA8, 0, 0, pf);
+}
+static int frame_fail(int code, const char *who, const char *why) { return xr_fail(code, (std::string(who) + ": " + why).c_str()); }
+// bad_format: what describe_pixel_format / describe_channels said about the entry point's format arguments
+static int check_frame(const char *who, const xrhip_image *im, const FrameSource &s, const char *bad_format) {
+    if (!im) return frame_fail(XRHIP_EINVAL, who, "img is null");
+    if (!s.pixels) return frame_fail(XRHIP_EINVAL, who, "pixels is null");
+    if (bad_format) return frame_fail(XRHIP_EINVAL, who, bad_format);
+    if (s.scaled) {
+        if (const char *why = xrh::check_frame_geometry(s.geo, im->ctx->w, im->ctx->h, s.pf.bpp, s.stride)) return frame_fail(XRHIP_EINVAL, who, why);
+    } else if ((long long)s.stride < (long long)im->ctx->w * s.pf.bpp) {
+        return frame_fail(XRHIP_EINVAL, who, "stride_bytes < width * bytes per pixel");
+    }
+    return XRHIP_OK;
+}
+// UploadArgs::fmt / ScaleArgs::fmt of a format (UPF_*, klt_kernels.hip.h); 0 for GRAY8 without a range flag, BGR8 and BGRA8
+static int upf_word(const xrh::PixelFormat &pf) {
+    return (pf.bpp == 2 ? (int)pf.shift | (pf.mask == 0xffu ? UPF_LOW_BYTE : 0) : 0) | (pf.rgb ? UPF_RGB : 0) | (pf.limited ? UPF_LIMITED : 0);
+}
+
+// Before a buffer the GPU may still be reading is freed to grow: everything the context has issued so far completes
+static int wait_before_growth(xrhip_klt *c) {
+    if (!c->group) {
+        XR_HIP(hipStreamSynchronize(c->stream));
+        return XRHIP_OK;
+    }
+    int rc = flush_upload(c);
+    if (rc) return rc;
+    rc = group_drain(c->group, GQ_KLT, c);
+    if (rc) return rc;
+    c->uploads_unsynced = 0;
+    return XRHIP_OK;
+}
+// The pinned slots hold a gray frame until the first larger frame arrives: a gray-only caller never pays for the colour size.
 static int ensure_slot_bytes(xrhip_klt *c, size_t bytes) {
     if (bytes <= c->up_cap) return XRHIP_OK;
-    // nothing may still be reading the slots that are about to go
-    if (c->group) {
-        int rc = flush_upload(c);
-        if (rc) return rc;
-        rc = group_drain(c->group, GQ_KLT, c);
-        if (rc) return rc;
-        c->uploads_unsynced = 0;
-    } else {
-        XR_HIP(hipStreamSynchronize(c->stream));
-    }
+    const int rc = wait_before_growth(c);
+    if (rc) return rc;
     for (int i = 0; i < xrhip_klt::UP_SLOTS; ++i) {
         hipHostFree(c->up_buf[i]);
         c->up_buf[i] = nullptr;
@@ -669,73 +711,207 @@ static int ensure_slot_bytes(xrhip_klt *c, size_t bytes) {
     c->up_cap = bytes;
     return XRHIP_OK;
 }
-
-// Copies a host frame into the next pinned slot and queues its transfer into `dst` (w*h, dense); the caller's buffer is free on return.
-// bpp 1: a gray frame, DMA (or the group's upload launch).  bpp 3 / 4: a BGR / BGRA frame, reduced to gray by k_upload, which reads
-// the mapped slot -- the plane in HBM is written once and the colour bytes cross the host link once.  The same for the other
-// pixel formats (fmt: UPF_*, klt_kernels.hip.h), rows of w * bpp bytes; a 1-byte format with fmt set goes through k_upload too.
-static int stage_host_frame(xrhip_klt *c, const uint8_t *pixels, int stride, uint8_t *dst, int bpp = 1, int fmt = 0) {
-    const size_t row = (size_t)c->w * bpp;
-    if (bpp != 1) {
-        const int rc = ensure_slot_bytes(c, row * c->h);
-        if (rc) return rc;
-    }
-    const int slot = c->up_next;
+// The next pinned slot, large enough and safe to overwrite, filled with `rows` rows of `row` bytes (`stride` apart at `src`, packed
+// in the slot): the caller's buffer is free on return.  slot_in_flight follows once the slot's reader has been queued.
+static int slot_fill(xrhip_klt *c, const uint8_t *src, int stride, size_t row, int rows, int &slot) {
+    const int rc = ensure_slot_bytes(c, row * rows);
+    if (rc) return rc;
+    slot = c->up_next;
     c->up_next = (slot + 1) % xrhip_klt::UP_SLOTS;
     if (c->group) {
         // the slot was read by the upload launched three frames ago; the pipeline has waited for two tracking results since (same
         // queue, in order).  A caller that uploads without ever waiting is held here instead.
         if (c->uploads_unsynced >= xrhip_klt::UP_SLOTS - 1) {
-            int rc = group_drain(c->group, GQ_KLT, c);
-            if (rc) return rc;
+            const int rd = group_drain(c->group, GQ_KLT, c);
+            if (rd) return rd;
             c->uploads_unsynced = 0;
         }
-        int rc = group_wait_launched(&c->rq_upload);   // (its argument block is about to be rewritten)
-        if (rc) return rc;
-        uint8_t *buf = c->up_buf[slot];
-        if ((size_t)stride == row) copy_to_pinned(buf, pixels, row * c->h);
-        else xrh::pack_rows(buf, pixels, stride, row, c->h);
-        uint8_t *dbuf = nullptr;
-        XR_HIP(hipHostGetDevicePointer((void **)&dbuf, buf, 0));
-        rc = flush_upload(c);   // (an earlier frame nobody preprocessed)
-        if (rc) return rc;
-        c->a_upload = UploadArgs{dbuf, (int)row, dst, c->w, c->h, bpp, fmt};
+    } else if (c->up_busy[slot]) {
+        XR_HIP(hipEventSynchronize(c->up_done[slot]));   // three uploads ago: long done unless nothing consumed them
+    }
+    if ((size_t)stride == row) copy_to_pinned(c->up_buf[slot], src, row * rows);
+    else xrh::pack_rows(c->up_buf[slot], src, stride, row, rows);
+    return XRHIP_OK;
+}
+static int slot_in_flight(xrhip_klt *c, int slot) {
+    if (c->group) {
         c->uploads_unsynced++;
-        c->upload_pending = true;   // submitted with the frame's preprocessing (xrhip_image_preprocess), or by whoever reads the plane first
         return XRHIP_OK;
-    }
-    if (c->up_busy[slot]) XR_HIP(hipEventSynchronize(c->up_done[slot]));   // three uploads ago: long done unless nothing consumed them
-    uint8_t *buf = c->up_buf[slot];
-    if ((size_t)stride == row) {
-        copy_to_pinned(buf, pixels, row * c->h);
-    } else {
-        xrh::pack_rows(buf, pixels, stride, row, c->h);
-    }
-    if (bpp == 1 && fmt == 0) {
-        XR_HIP(hipMemcpyAsync(dst, buf, (size_t)c->w * c->h, hipMemcpyHostToDevice, c->stream));
-    } else {
-        uint8_t *dbuf = nullptr;
-        XR_HIP(hipHostGetDevicePointer((void **)&dbuf, buf, 0));
-        c->a_upload = UploadArgs{dbuf, (int)row, dst, c->w, c->h, bpp, fmt};
-        const int rc = klt_issue(c, c->rq_upload, GK_UPLOAD, &c->a_upload, launch_upload_batch);
-        if (rc) return rc;
     }
     XR_HIP(hipEventRecord(c->up_done[slot], c->stream));
     c->up_busy[slot] = true;
     return XRHIP_OK;
 }
 
-int xrhip_image_upload(xrhip_image *im, const uint8_t *gray, int stride) {
-    if (!im || !gray || stride < im->ctx->w) return xr_fail(XRHIP_EINVAL, "xrhip_image_upload: bad arguments");
-    xrhip_klt *c = im->ctx;
-    // the host buffer may be reused by the caller as soon as we return (PushImage deep-copies)
-    const int rc = stage_host_frame(c, gray, stride, im->raw);
+// A k_upload request.  A group member's is deferred: it is submitted with the frame's preprocessing (xrhip_image_preprocess), or by
+// whoever reads the plane first.  A context on its own launches it here and now.
+static int queue_upload(xrhip_klt *c, const UploadArgs &a) {
+    if (c->group) {
+        int rc = group_wait_launched(&c->rq_upload);   // (its argument block is about to be rewritten)
+        if (rc) return rc;
+        if (c->upload_pending) {   // an earlier frame nobody preprocessed goes out on its own -- and reads the block before it changes
+            rc = flush_upload(c);
+            if (rc) return rc;
+            rc = group_wait_launched(&c->rq_upload);
+            if (rc) return rc;
+        }
+        c->a_upload = a;
+        c->upload_pending = true;
+        return XRHIP_OK;
+    }
+    c->a_upload = a;
+    return klt_issue(c, c->rq_upload, GK_UPLOAD, &c->a_upload, launch_upload_batch);
+}
+// A frame of the plane's size into `dst` (w*h, dense).  8-bit gray on a context of its own is a copy: DMA from the pinned slot, or
+// device to device.  Everything else is a k_upload request (fmt: UPF_*), which reduces the other formats to gray as it reads -- a host
+// frame from the mapped slot, so the plane in HBM is written once and the frame's bytes cross the host link once.
+static int upload_into(xrhip_klt *c, const FrameSource &s, uint8_t *dst) {
+    const int bpp = s.pf.bpp, fmt = upf_word(s.pf);
+    const bool copy = !c->group && bpp == 1 && fmt == 0;
+    if (s.on_device) {
+        if (!copy) return queue_upload(c, UploadArgs{s.pixels, s.stride, dst, c->w, c->h, bpp, fmt});
+        XR_HIP(hipMemcpy2DAsync(dst, c->w, s.pixels, s.stride, c->w, c->h, hipMemcpyDeviceToDevice, c->stream));
+        return XRHIP_OK;
+    }
+    const size_t row = (size_t)c->w * bpp;
+    int slot = 0;
+    int rc = slot_fill(c, s.pixels, s.stride, row, c->h, slot);
     if (rc) return rc;
+    uint8_t *buf = c->up_buf[slot];
+    if (copy) {
+        XR_HIP(hipMemcpyAsync(dst, buf, row * c->h, hipMemcpyHostToDevice, c->stream));
+    } else {
+        uint8_t *dbuf = nullptr;
+        XR_HIP(hipHostGetDevicePointer((void **)&dbuf, buf, 0));
+        rc = queue_upload(c, UploadArgs{dbuf, (int)row, dst, c->w, c->h, bpp, fmt});
+        if (rc) return rc;
+    }
+    return slot_in_flight(c, slot);
+}
+
+// The crop of a frame of any pixel format, area-averaged down to the context's plane (k_upload_scaled) on the way in.  A frame in HBM
+// is read where it lies.  A host frame: only the crop is staged (rows of cw * bpp bytes, packed) through the pinned slots, which grow
+// as they do for colour; the slot is then copied to an HBM scratch and the kernel reads that.  Neighbouring plane pixels share
+// source pixels and a plane row's footprint rows are read by several wavefronts, so a kernel reading the mapped slot would fetch
+// bytes over the host link more than once unless every repeat hit a cache -- nothing guarantees that for host memory; the copy costs
+// one HBM write and read of the crop and makes "once over the link" hold by construction.
+// Not part of the shared upload launch: like the undistortion remap it is a launch of its own, in the context's order (a group
+// member: on the group's front-end queue, behind a pending upload, which is submitted first).
+static int upload_scaled_into(xrhip_klt *c, const FrameSource &s, uint8_t *dst) {
+    const int cw = s.geo->crop_width, ch = s.geo->crop_height;
+    ScaleArgs a{};
+    a.src = xrh::crop_origin(s.pixels, s.stride, *s.geo, s.pf.bpp);
+    a.sstride = s.stride;
+    a.dst = dst;
+    a.w = c->w;
+    a.h = c->h;
+    a.bpp = s.pf.bpp;
+    a.fmt = upf_word(s.pf);
+    a.cw = cw;
+    a.ch = ch;
+    a.wide = ((uint64_t)c->w * (uint64_t)cw >> 32) != 0 || ((uint64_t)c->h * (uint64_t)ch >> 32) != 0;
+    const unsigned n4 = (unsigned)(((size_t)c->w * c->h + 3) / 4);
+    const dim3 grid(std::max(1u, std::min((n4 + 255u) / 256u, 2048u)));
+    const size_t row = (size_t)cw * s.pf.bpp, bytes = row * ch;
+    const uint8_t *staged = nullptr;   // host frame: the slot that holds the crop
+    int slot = 0;
+    if (!s.on_device) {
+        int rc = XRHIP_OK;
+        if (bytes > c->scale_cap) {
+            rc = wait_before_growth(c);
+            if (rc) return rc;
+            hipFree(c->scale_src);
+            c->scale_src = nullptr;
+            c->scale_cap = 0;
+            XR_HIP(hipMalloc(&c->scale_src, bytes));
+            c->scale_cap = bytes;
+        }
+        rc = slot_fill(c, a.src, s.stride, row, ch, slot);
+        if (rc) return rc;
+        staged = c->up_buf[slot];
+        a.src = c->scale_src;
+        a.sstride = (int)row;
+    }
+    const int rc = klt_run(c, [=](hipStream_t st) {
+        if (staged) XR_HIP(hipMemcpyAsync(c->scale_src, staged, bytes, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_upload_scaled, grid, dim3(256), 0, st, a);
+        XR_HIP(hipGetLastError());
+        return XRHIP_OK;
+    });
+    if (rc || !staged) return rc;
+    return slot_in_flight(c, slot);
+}
+
+// Every xrhip_image_upload* entry point (`who`).  distorted: the frame is as the camera recorded it and k_undistort rectifies it into
+// the plane -- reduced / scaled into undist_src first, rectified second: the gray frame takes the place of the one a gray camera of
+// the plane's size would have recorded; such a frame already in HBM is remapped where it lies.
+static int upload_frame(xrhip_image *im, const FrameSource &s, const char *bad_format, bool distorted, const char *who) {
+    int rc = check_frame(who, im, s, bad_format);
+    if (rc) return rc;
+    xrhip_klt *c = im->ctx;
+    if (distorted && !c->have_undist) return frame_fail(XRHIP_ESTATE, who, "no undistortion map (xrhip_klt_set_undistort_map)");
+    const uint8_t *remap_src = c->undist_src;
+    int remap_stride = c->w;
+    if (distorted && s.on_device && !s.scaled && s.pf.bpp == 1 && upf_word(s.pf) == 0) {
+        remap_src = s.pixels;
+        remap_stride = s.stride;
+    } else {
+        // (a host buffer may be reused by the caller as soon as we return: PushImage deep-copies, the pinned slot holds our copy)
+        uint8_t *dst = distorted ? c->undist_src : im->raw;
+        rc = s.scaled ? upload_scaled_into(c, s, dst) : upload_into(c, s, dst);
+        if (rc) return rc;
+    }
+    if (distorted) {   // (not batched: a remap per frame on a path the bench's resident / rectified inputs do not take)
+        rc = klt_run(c, [=](hipStream_t st) {
+            hipLaunchKernelGGL(k_undistort, dim3((c->w + 63) / 64, (c->h + 3) / 4), dim3(256), 0, st, remap_src, remap_stride,
+                               (const uint2 *)c->undist_map, im->raw, c->w, c->w, c->h);
+            XR_HIP(hipGetLastError());
+            return XRHIP_OK;
+        });
+        if (rc) return rc;
+    }
     im->have_raw = true;
     im->have_pyramid = false;
     im->want_detect = false;
     im->detect_seq = 0;
     return XRHIP_OK;
+}
+
+int xrhip_image_upload(xrhip_image *im, const uint8_t *gray, int stride) {
+    return upload_frame(im, frame_source(gray, stride, 0), nullptr, false, "xrhip_image_upload");
+}
+int xrhip_image_upload_device(xrhip_image *im, const void *gray_dev, int stride) {
+    return upload_frame(im, frame_source(gray_dev, stride, 1), nullptr, false, "xrhip_image_upload_device");
+}
+int xrhip_image_upload_distorted(xrhip_image *im, const void *gray, int stride, int on_device) {
+    return upload_frame(im, frame_source(gray, stride, on_device), nullptr, true, "xrhip_image_upload_distorted");
+}
+int xrhip_image_upload_color(xrhip_image *im, const void *pixels, int stride, int channels, int on_device) {
+    FrameSource s = frame_source(pixels, stride, on_device);
+    return upload_frame(im, s, describe_channels(channels, s.pf), false, "xrhip_image_upload_color");
+}
+int xrhip_image_upload_color_distorted(xrhip_image *im, const void *pixels, int stride, int channels, int on_device) {
+    FrameSource s = frame_source(pixels, stride, on_device);
+    return upload_frame(im, s, describe_channels(channels, s.pf), true, "xrhip_image_upload_color_distorted");
+}
+// The pixel formats (xrslam_hip.h: XRHIP_PIXFMT_*): GRAY8 without a range flag, BGR8 and BGRA8 are the older entry points' frames
+int xrhip_image_upload_format(xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited, int on_device) {
+    FrameSource s = frame_source(pixels, stride, on_device);
+    return upload_frame(im, s, xrh::describe_pixel_format(format, bits, limited, s.pf), false, "xrhip_image_upload_format");
+}
+int xrhip_image_upload_format_distorted(xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited, int on_device) {
+    FrameSource s = frame_source(pixels, stride, on_device);
+    return upload_frame(im, s, xrh::describe_pixel_format(format, bits, limited, s.pf), true, "xrhip_image_upload_format_distorted");
+}
+int xrhip_image_upload_scaled(xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited, int on_device,
+                              const xrhip_frame_geometry *geo) {
+    FrameSource s = frame_source(pixels, stride, on_device, geo, true);
+    return upload_frame(im, s, xrh::describe_pixel_format(format, bits, limited, s.pf), false, "xrhip_image_upload_scaled");
+}
+int xrhip_image_upload_scaled_distorted(xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited, int on_device,
+                                        const xrhip_frame_geometry *geo) {
+    FrameSource s = frame_source(pixels, stride, on_device, geo, true);
+    return upload_frame(im, s, xrh::describe_pixel_format(format, bits, limited, s.pf), true, "xrhip_image_upload_scaled_distorted");
 }
 
 int xrhip_klt_set_undistort_map(xrhip_klt *c, const uint32_t *map2) {
@@ -755,35 +931,6 @@ int xrhip_klt_set_undistort_map(xrhip_klt *c, const uint32_t *map2) {
     });
     if (rc) return rc;
     c->have_undist = true;
-    return XRHIP_OK;
-}
-
-int xrhip_image_upload_distorted(xrhip_image *im, const void *gray, int stride, int on_device) {
-    if (!im || !gray || stride < im->ctx->w) return xr_fail(XRHIP_EINVAL, "xrhip_image_upload_distorted: bad arguments");
-    xrhip_klt *c = im->ctx;
-    if (!c->have_undist) return xr_fail(XRHIP_ESTATE, "xrhip_image_upload_distorted: no undistortion map (xrhip_klt_set_undistort_map)");
-    const uint8_t *src = static_cast<const uint8_t *>(gray);
-    int sstride = stride;
-    if (!on_device) {   // one upload of the frame as the camera recorded it; the remap below reads it in HBM
-        const int rc = stage_host_frame(c, static_cast<const uint8_t *>(gray), stride, c->undist_src);
-        if (rc) return rc;
-        src = c->undist_src;
-        sstride = c->w;
-    }
-    {   // (not batched: a remap per frame on a path the bench's resident / rectified inputs do not take)
-        int rc = klt_run(c, [=](hipStream_t st) {
-            hipLaunchKernelGGL(k_undistort, dim3((c->w + 63) / 64, (c->h + 3) / 4), dim3(256), 0, st, src, sstride,
-                               (const uint2 *)c->undist_map, im->raw, c->w, c->w, c->h);
-            XR_HIP(hipGetLastError());
-            return XRHIP_OK;
-        });
-        if (rc) return rc;
-    }
-    // (a host buffer may be reused by the caller as soon as we return: stage_host_frame has copied it)
-    im->have_raw = true;
-    im->have_pyramid = false;
-    im->want_detect = false;
-    im->detect_seq = 0;
     return XRHIP_OK;
 }
 
@@ -818,236 +965,6 @@ int xrhip_debug_get_raw(xrhip_image *im, uint8_t *out) {
         XR_HIP(hipMemcpyAsync(out, im->raw, (size_t)c->w * c->h, hipMemcpyDeviceToHost, st));
         return XRHIP_OK;
     });
-}
-
-int xrhip_image_upload_device(xrhip_image *im, const void *gray_dev, int stride) {
-    if (!im || !gray_dev || stride < im->ctx->w) return xr_fail(XRHIP_EINVAL, "xrhip_image_upload_device: bad arguments");
-    xrhip_klt *c = im->ctx;
-    if (c->group) {
-        int rc = group_wait_launched(&c->rq_upload);
-        if (rc) return rc;
-        rc = flush_upload(c);
-        if (rc) return rc;
-        c->a_upload = UploadArgs{static_cast<const uint8_t *>(gray_dev), stride, im->raw, c->w, c->h};
-        c->upload_pending = true;
-    } else {
-        XR_HIP(hipMemcpy2DAsync(im->raw, c->w, gray_dev, stride, c->w, c->h, hipMemcpyDeviceToDevice, c->stream));
-    }
-    im->have_raw = true;
-    im->have_pyramid = false;
-    im->want_detect = false;
-    im->detect_seq = 0;
-    return XRHIP_OK;
-}
-
-// A BGR / BGRA frame (or, with fmt, a frame of another pixel format of `channels` bytes per pixel) into `dst` as gray: from a host
-// buffer through the pinned slots, or from HBM where it lies
-static int upload_color_into(xrhip_klt *c, const void *pixels, int stride, int channels, int on_device, uint8_t *dst, int fmt = 0) {
-    if (!on_device) return stage_host_frame(c, static_cast<const uint8_t *>(pixels), stride, dst, channels, fmt);
-    if (c->group) {
-        int rc = group_wait_launched(&c->rq_upload);
-        if (rc) return rc;
-        rc = flush_upload(c);
-        if (rc) return rc;
-    }
-    c->a_upload = UploadArgs{static_cast<const uint8_t *>(pixels), stride, dst, c->w, c->h, channels, fmt};
-    if (c->group) {
-        c->upload_pending = true;   // with the frame's preprocessing, like xrhip_image_upload_device
-        return XRHIP_OK;
-    }
-    return klt_issue(c, c->rq_upload, GK_UPLOAD, &c->a_upload, launch_upload_batch);
-}
-static int check_color_args(const char *who, const xrhip_image *im, const void *pixels, int stride, int channels) {
-    if (!im || !pixels) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": null argument").c_str());
-    if (channels != 3 && channels != 4) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": channels must be 1, 3 (BGR) or 4 (BGRA)").c_str());
-    if ((long long)stride < (long long)im->ctx->w * channels) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": stride_bytes < width * channels").c_str());
-    return XRHIP_OK;
-}
-
-int xrhip_image_upload_color(xrhip_image *im, const void *pixels, int stride, int channels, int on_device) {
-    if (channels == 1 && im && pixels)
-        return on_device ? xrhip_image_upload_device(im, pixels, stride) : xrhip_image_upload(im, static_cast<const uint8_t *>(pixels), stride);
-    int rc = check_color_args("xrhip_image_upload_color", im, pixels, stride, channels);
-    if (rc) return rc;
-    rc = upload_color_into(im->ctx, pixels, stride, channels, on_device, im->raw);
-    if (rc) return rc;
-    im->have_raw = true;
-    im->have_pyramid = false;
-    im->want_detect = false;
-    im->detect_seq = 0;
-    return XRHIP_OK;
-}
-
-int xrhip_image_upload_color_distorted(xrhip_image *im, const void *pixels, int stride, int channels, int on_device) {
-    if (channels == 1 && im && pixels) return xrhip_image_upload_distorted(im, pixels, stride, on_device);
-    int rc = check_color_args("xrhip_image_upload_color_distorted", im, pixels, stride, channels);
-    if (rc) return rc;
-    xrhip_klt *c = im->ctx;
-    if (!c->have_undist) return xr_fail(XRHIP_ESTATE, "xrhip_image_upload_color_distorted: no undistortion map (xrhip_klt_set_undistort_map)");
-    // gray first, rectified second: the reduced frame takes the place of the frame a gray camera would have recorded
-    rc = upload_color_into(c, pixels, stride, channels, on_device, c->undist_src);
-    if (rc) return rc;
-    return xrhip_image_upload_distorted(im, c->undist_src, c->w, 1);
-}
-
-// The pixel formats (xrslam_hip.h: XRHIP_PIXFMT_*): GRAY8 without a range flag, BGR8 and BGRA8 are the older entry points' frames;
-// every other one is a k_upload request of its bytes per pixel and UPF_* word
-static int check_format_args(const char *who, const xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited,
-                             xrh::PixelFormat &pf) {
-    if (!im || !pixels) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": null argument").c_str());
-    if (const char *why = xrh::describe_pixel_format(format, bits, limited, pf)) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": " + why).c_str());
-    if ((long long)stride < (long long)im->ctx->w * pf.bpp) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": stride_bytes < width * bytes per pixel").c_str());
-    return XRHIP_OK;
-}
-static int upf_word(const xrh::PixelFormat &pf) {
-    return (pf.bpp == 2 ? (int)pf.shift | (pf.mask == 0xffu ? UPF_LOW_BYTE : 0) : 0) | (pf.rgb ? UPF_RGB : 0) | (pf.limited ? UPF_LIMITED : 0);
-}
-
-int xrhip_image_upload_format(xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited, int on_device) {
-    xrh::PixelFormat pf;
-    int rc = check_format_args("xrhip_image_upload_format", im, pixels, stride, format, bits, limited, pf);
-    if (rc) return rc;
-    const int fmt = upf_word(pf);
-    if (fmt == 0 && pf.bpp != 2) return xrhip_image_upload_color(im, pixels, stride, pf.bpp, on_device);   // gray, BGR, BGRA
-    rc = upload_color_into(im->ctx, pixels, stride, pf.bpp, on_device, im->raw, fmt);
-    if (rc) return rc;
-    im->have_raw = true;
-    im->have_pyramid = false;
-    im->want_detect = false;
-    im->detect_seq = 0;
-    return XRHIP_OK;
-}
-
-int xrhip_image_upload_format_distorted(xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited, int on_device) {
-    xrh::PixelFormat pf;
-    int rc = check_format_args("xrhip_image_upload_format_distorted", im, pixels, stride, format, bits, limited, pf);
-    if (rc) return rc;
-    const int fmt = upf_word(pf);
-    if (fmt == 0 && pf.bpp != 2) return xrhip_image_upload_color_distorted(im, pixels, stride, pf.bpp, on_device);
-    xrhip_klt *c = im->ctx;
-    if (!c->have_undist) return xr_fail(XRHIP_ESTATE, "xrhip_image_upload_format_distorted: no undistortion map (xrhip_klt_set_undistort_map)");
-    rc = upload_color_into(c, pixels, stride, pf.bpp, on_device, c->undist_src, fmt);   // reduced first, rectified second
-    if (rc) return rc;
-    return xrhip_image_upload_distorted(im, c->undist_src, c->w, 1);
-}
-
-// ---------------------------------------------------------------------------------------------- frames larger than the working plane
-// The crop of a frame of any pixel format, area-averaged down to the context's plane (k_upload_scaled) on the way in.  A frame in HBM
-// is read where it lies.  A host frame: only the crop is staged (rows of cw * bpp bytes, packed) through the pinned slots, which grow
-// as they do for colour; the slot is then copied to an HBM scratch and the kernel reads that.  Neighbouring plane pixels share
-// source pixels and a plane row's footprint rows are read by several wavefronts, so a kernel reading the mapped slot would fetch
-// bytes over the host link more than once unless every repeat hit a cache -- nothing guarantees that for host memory; the copy costs
-// one HBM write and read of the crop and makes "once over the link" hold by construction.
-// Not part of the shared upload launch: like the undistortion remap it is a launch of its own, in the context's order (a group
-// member: on the group's front-end queue, behind a pending upload, which is submitted first).
-static int check_scaled_args(const char *who, const xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited,
-                             const xrhip_frame_geometry *geo, xrh::PixelFormat &pf) {
-    if (!im) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": img is null").c_str());
-    if (!pixels) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": pixels is null").c_str());
-    if (const char *why = xrh::describe_pixel_format(format, bits, limited, pf)) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": " + why).c_str());
-    if (const char *why = xrh::check_frame_geometry(geo, im->ctx->w, im->ctx->h, pf.bpp, stride)) return xr_fail(XRHIP_EINVAL, (std::string(who) + ": " + why).c_str());
-    return XRHIP_OK;
-}
-static int upload_scaled_into(xrhip_klt *c, const void *pixels, int stride, const xrh::PixelFormat &pf, int on_device,
-                              const xrhip_frame_geometry &g, uint8_t *dst) {
-    const int cw = g.crop_width, ch = g.crop_height;
-    const uint8_t *origin = xrh::crop_origin(static_cast<const uint8_t *>(pixels), stride, g, pf.bpp);
-    ScaleArgs a{};
-    a.dst = dst;
-    a.w = c->w;
-    a.h = c->h;
-    a.bpp = pf.bpp;
-    a.fmt = upf_word(pf);
-    a.cw = cw;
-    a.ch = ch;
-    a.wide = ((uint64_t)c->w * (uint64_t)cw >> 32) != 0 || ((uint64_t)c->h * (uint64_t)ch >> 32) != 0;
-    const unsigned n4 = (unsigned)(((size_t)c->w * c->h + 3) / 4);
-    const dim3 grid(std::max(1u, std::min((n4 + 255u) / 256u, 2048u)));
-    if (on_device) {
-        a.src = origin;
-        a.sstride = stride;
-        return klt_run(c, [=](hipStream_t st) {
-            hipLaunchKernelGGL(k_upload_scaled, grid, dim3(256), 0, st, a);
-            XR_HIP(hipGetLastError());
-            return XRHIP_OK;
-        });
-    }
-    const size_t row = (size_t)cw * pf.bpp, bytes = row * ch;
-    int rc = ensure_slot_bytes(c, bytes);
-    if (rc) return rc;
-    if (bytes > c->scale_cap) {
-        // nothing may still be reading the scratch that is about to go
-        if (c->group) {
-            rc = flush_upload(c);
-            if (rc) return rc;
-            rc = group_drain(c->group, GQ_KLT, c);
-            if (rc) return rc;
-            c->uploads_unsynced = 0;
-        } else {
-            XR_HIP(hipStreamSynchronize(c->stream));
-        }
-        hipFree(c->scale_src);
-        c->scale_src = nullptr;
-        c->scale_cap = 0;
-        XR_HIP(hipMalloc(&c->scale_src, bytes));
-        c->scale_cap = bytes;
-    }
-    const int slot = c->up_next;
-    c->up_next = (slot + 1) % xrhip_klt::UP_SLOTS;
-    if (c->group) {   // (the slots' reuse: as in stage_host_frame)
-        if (c->uploads_unsynced >= xrhip_klt::UP_SLOTS - 1) {
-            rc = group_drain(c->group, GQ_KLT, c);
-            if (rc) return rc;
-            c->uploads_unsynced = 0;
-        }
-    } else if (c->up_busy[slot]) {
-        XR_HIP(hipEventSynchronize(c->up_done[slot]));
-    }
-    uint8_t *buf = c->up_buf[slot];
-    if ((size_t)stride == row) copy_to_pinned(buf, origin, bytes);
-    else xrh::pack_rows(buf, origin, stride, row, ch);
-    a.src = c->scale_src;
-    a.sstride = (int)row;
-    rc = klt_run(c, [=](hipStream_t st) {
-        XR_HIP(hipMemcpyAsync(c->scale_src, buf, bytes, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_upload_scaled, grid, dim3(256), 0, st, a);
-        XR_HIP(hipGetLastError());
-        return XRHIP_OK;
-    });
-    if (rc) return rc;
-    if (c->group) {
-        c->uploads_unsynced++;
-    } else {
-        XR_HIP(hipEventRecord(c->up_done[slot], c->stream));
-        c->up_busy[slot] = true;
-    }
-    return XRHIP_OK;
-}
-
-int xrhip_image_upload_scaled(xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited, int on_device,
-                              const xrhip_frame_geometry *geo) {
-    xrh::PixelFormat pf;
-    int rc = check_scaled_args("xrhip_image_upload_scaled", im, pixels, stride, format, bits, limited, geo, pf);
-    if (rc) return rc;
-    rc = upload_scaled_into(im->ctx, pixels, stride, pf, on_device, *geo, im->raw);
-    if (rc) return rc;
-    im->have_raw = true;
-    im->have_pyramid = false;
-    im->want_detect = false;
-    im->detect_seq = 0;
-    return XRHIP_OK;
-}
-
-int xrhip_image_upload_scaled_distorted(xrhip_image *im, const void *pixels, int stride, int format, int bits, int limited, int on_device,
-                                        const xrhip_frame_geometry *geo) {
-    xrh::PixelFormat pf;
-    int rc = check_scaled_args("xrhip_image_upload_scaled_distorted", im, pixels, stride, format, bits, limited, geo, pf);
-    if (rc) return rc;
-    xrhip_klt *c = im->ctx;
-    if (!c->have_undist) return xr_fail(XRHIP_ESTATE, "xrhip_image_upload_scaled_distorted: no undistortion map (xrhip_klt_set_undistort_map)");
-    rc = upload_scaled_into(c, pixels, stride, pf, on_device, *geo, c->undist_src);   // scaled first, rectified second
-    if (rc) return rc;
-    return xrhip_image_upload_distorted(im, c->undist_src, c->w, 1);
 }
 
 /* measurement aid: HIP-event time of whatever the context issues between phase 0 and phase 1 (which waits for it) */

@@ -1456,6 +1456,11 @@ template <int ND> __device__ __forceinline__ void load_dwords_unaligned(uintptr_
         for (int k = 0; k < ND; ++k) d[k] = (d[k] >> sh) | (d[k + 1] << (32u - sh));
     }
 }
+// the gray value of the one pixel at `s`, byte by byte
+template <int BPP> __device__ __forceinline__ uint32_t gray1(const uint8_t *s, uint32_t w0, uint32_t w2, uint32_t mask, uint32_t shift, bool limited) {
+    if (BPP >= 3) return bgr_to_gray(s[0], s[1], s[2], w0, w2);
+    return narrow_to_gray(BPP == 2 ? (uint32_t)s[0] | ((uint32_t)s[BPP - 1] << 8) : (uint32_t)s[0], mask, shift, limited);
+}
 // A frame of BPP bytes per pixel (any base alignment, any stride >= w * BPP) reduced into the dense gray plane.  A lane owns four
 // consecutive pixels of the plane = one dword store.  Where the four lie in one row it fetches the aligned dwords that cover their
 // 4 * BPP source bytes -- neighbouring lanes read neighbouring dwords (BPP 2: a wavefront's loads cover 512 contiguous bytes), and
@@ -1503,9 +1508,7 @@ template <int BPP> __device__ __forceinline__ void d_upload_reduce(const UploadA
             const uint32_t pe = p0 + 4u < total ? p0 + 4u : total;
             for (uint32_t p = p0; p < pe; ++p) {
                 const uint32_t py = p / w, px = p - py * w;
-                const uint8_t *s = a.src + (size_t)py * (size_t)a.sstride + (size_t)px * BPP;
-                if (BPP >= 3) a.dst[p] = (uint8_t)bgr_to_gray(s[0], s[1], s[2], w0, w2);
-                else a.dst[p] = (uint8_t)narrow_to_gray(BPP == 2 ? (uint32_t)s[0] | ((uint32_t)s[BPP - 1] << 8) : (uint32_t)s[0], mask, shift, limited);
+                a.dst[p] = (uint8_t)gray1<BPP>(a.src + (size_t)py * (size_t)a.sstride + (size_t)px * BPP, w0, w2, mask, shift, limited);
             }
         }
     }
@@ -1623,12 +1626,7 @@ template <int BPP, int N> __device__ __forceinline__ void d_scale_pixels(const S
 #pragma unroll
             for (int q = 0; q < 4; ++q) scale_add<N>(r, s + q * w, w, cw, g[q]);
         }
-        for (; s < end; s += w, p += BPP) {
-            uint32_t g;
-            if (BPP >= 3) g = bgr_to_gray(p[0], p[1], p[2], w0, w2);
-            else g = narrow_to_gray(BPP == 2 ? (uint32_t)p[0] | ((uint32_t)p[BPP - 1] << 8) : (uint32_t)p[0], mask, shift, limited);
-            scale_add<N>(r, s, w, cw, g);
-        }
+        for (; s < end; s += w, p += BPP) scale_add<N>(r, s, w, cw, gray1<BPP>(p, w0, w2, mask, shift, limited));
 #pragma unroll
         for (int k = 0; k < N; ++k) acc[k] += b * r[k];
     }

@@ -335,34 +335,39 @@ class Session:
             k += 1
         self.imu_k = k
 
+    def _route(self):
+        """How this session's frames reach the library, from what it holds now (channels / pixel_format / geometry may be set between
+        steps): (push(ptr, stride, on_dev, t), name of the replay entry point, the arguments it takes between stride and on_device)."""
+        api, ch = self.api, self.channels
+        fmt = None if self.pixel_format is None else C.byref(self.pixel_format)
+        if self.geometry is not None:
+            geo = C.byref(self.geometry)
+            return (lambda p, s, d, t: api.push_image_scaled(p, s, fmt, geo, d, t)), "XRSLAMAmdInstanceReplayScaled", (fmt, geo)
+        if fmt is not None:
+            return (lambda p, s, d, t: api.push_image_format(p, s, fmt, d, t)), "XRSLAMAmdInstanceReplayFormat", (fmt,)
+
+        def push(p, s, d, t):
+            if not d:
+                api.push(XRSLAM_SENSOR_CAMERA, C.byref(XRSLAMImage(p.value, t, s, 0, ch, None)))
+            elif ch == 1:
+                api.push_image_device(p, s, t)
+            else:
+                api.push_image_device_color(p, s, ch, t)
+        return (push, "XRSLAMAmdInstanceReplay", ()) if ch == 1 else (push, "XRSLAMAmdInstanceReplayColor", (ch,))
+
     def step(self):
         """Feeds everything up to and including the next camera frame; returns False at the end."""
         if self.frame_k >= len(self.seq["cam_t"]):
             return False
         t = float(self.seq["cam_t"][self.frame_k])
         self._push_imu_until(t)
-        if self.pixel_format is not None or self.geometry is not None:
-            if self.device_frames is not None:
-                base, fbytes, stride = self.device_frames
-                ptr, on_dev = C.c_void_p(base + self.frame_k * fbytes), 1
-            else:
-                fr = self.seq["frames"][self.frame_k]
-                ptr, stride, on_dev = C.c_void_p(fr.ctypes.data), fr.strides[0], 0
-            if self.geometry is not None:
-                self.api.push_image_scaled(ptr, stride, None if self.pixel_format is None else C.byref(self.pixel_format),
-                                           C.byref(self.geometry), on_dev, t)
-            else:
-                self.api.push_image_format(ptr, stride, C.byref(self.pixel_format), on_dev, t)
-        elif self.device_frames is not None:
+        if self.device_frames is not None:
             base, fbytes, stride = self.device_frames
-            if self.channels == 1:
-                self.api.push_image_device(C.c_void_p(base + self.frame_k * fbytes), stride, t)
-            else:
-                self.api.push_image_device_color(C.c_void_p(base + self.frame_k * fbytes), stride, self.channels, t)
+            ptr, on_dev = C.c_void_p(base + self.frame_k * fbytes), 1
         else:
             fr = self.seq["frames"][self.frame_k]
-            img = XRSLAMImage(fr.ctypes.data, t, fr.strides[0], 0, self.channels, None)
-            self.api.push(XRSLAM_SENSOR_CAMERA, C.byref(img))
+            ptr, stride, on_dev = C.c_void_p(fr.ctypes.data), fr.strides[0], 0
+        self._route()[0](ptr, stride, on_dev, t)
         self.api.run()
         state = C.c_int(-1)
         self.api.get_result(XRSLAM_RESULT_STATE, C.byref(state))
@@ -389,21 +394,9 @@ class Session:
             ptr, on_dev = C.c_void_p(base), 1
         else:
             ptr, fbytes, stride, on_dev = C.c_void_p(frames.ctypes.data), frames.strides[0], frames.strides[1], 0
-        if self.geometry is not None:
-            k = self.lib.XRSLAMAmdInstanceReplayScaled(self._handle, imu.ctypes.data, len(imu), cam_t.ctypes.data, len(cam_t), ptr,
-                                                       fbytes, stride, None if self.pixel_format is None else C.byref(self.pixel_format),
-                                                       C.byref(self.geometry), on_dev, C.byref(ic), C.byref(fc), int(n), out.ctypes.data)
-        elif self.pixel_format is not None:
-            k = self.lib.XRSLAMAmdInstanceReplayFormat(self._handle, imu.ctypes.data, len(imu), cam_t.ctypes.data, len(cam_t), ptr,
-                                                       fbytes, stride, C.byref(self.pixel_format), on_dev, C.byref(ic), C.byref(fc),
-                                                       int(n), out.ctypes.data)
-        elif self.channels == 1:
-            k = self.lib.XRSLAMAmdInstanceReplay(self._handle, imu.ctypes.data, len(imu), cam_t.ctypes.data, len(cam_t), ptr, fbytes,
-                                                 stride, on_dev, C.byref(ic), C.byref(fc), int(n), out.ctypes.data)
-        else:
-            k = self.lib.XRSLAMAmdInstanceReplayColor(self._handle, imu.ctypes.data, len(imu), cam_t.ctypes.data, len(cam_t), ptr,
-                                                      fbytes, stride, self.channels, on_dev, C.byref(ic), C.byref(fc), int(n),
-                                                      out.ctypes.data)
+        _, replay, extra = self._route()
+        k = getattr(self.lib, replay)(self._handle, imu.ctypes.data, len(imu), cam_t.ctypes.data, len(cam_t), ptr, fbytes, stride, *extra,
+                                      on_dev, C.byref(ic), C.byref(fc), int(n), out.ctypes.data)
         if k < 0:
             raise RuntimeError("XRSLAMAmdInstanceReplay: bad arguments")
         self.imu_k, self.frame_k = ic.value, fc.value

@@ -177,64 +177,55 @@ class HipImage:
     def upload_distorted_device(self, dev_ptr, stride):
         check(L().xrhip_image_upload_distorted(self._h, C.c_void_p(dev_ptr), int(stride), 1))
 
-    def _color_args(self, pixels, on_device, stride, channels):
-        if on_device:   # pixels: a device pointer (int) to interleaved BGR / BGRA rows
-            return C.c_void_p(int(pixels)), int(stride), int(channels)
-        assert pixels.dtype == np.uint8 and pixels.ndim == 3 and pixels.shape[:2] == (self.ctx.h, self.ctx.w), pixels.shape
-        assert pixels.strides[2] == 1 and pixels.strides[1] == pixels.shape[2], pixels.strides   # rows may be padded, pixels not
-        return _p(pixels), pixels.strides[0], pixels.shape[2]
+    def _frame_args(self, pixels, on_device, stride, rows=None, interleaved=False):
+        """-> (pointer, row stride in bytes) of a frame of `rows` rows (default: the plane's).  on_device: `pixels` is a device pointer
+        (int) to row 0 and `stride` its row stride.  Otherwise a uint8 array of the frame's bytes, [rows][row bytes] or [rows][w][bytes
+        per pixel] (interleaved: the latter, as wide as the plane); rows may be padded, pixels not."""
+        if on_device:
+            return C.c_void_p(int(pixels)), int(stride)
+        assert pixels.dtype == np.uint8 and pixels.ndim in (2, 3) and pixels.shape[0] == (rows or self.ctx.h), pixels.shape
+        assert not interleaved or (pixels.ndim == 3 and pixels.shape[1] == self.ctx.w), pixels.shape
+        assert pixels.strides[-1] == 1 and (pixels.ndim == 2 or pixels.strides[1] == pixels.shape[2]), pixels.strides
+        return _p(pixels), pixels.strides[0]
+
+    def _upload(self, fn, pixels, on_device, stride, *more, **how):
+        ptr, stride = self._frame_args(pixels, on_device, stride, **how)
+        check(fn(self._h, ptr, stride, *more))
 
     def upload_color(self, pixels, on_device=False, stride=None, channels=None):
         """An interleaved BGR / BGRA frame, reduced to gray on its way in: a uint8 array [h][w][3 or 4] (rows may be strided),
         or -- on_device -- a device pointer with its row stride in bytes and its channel count."""
-        ptr, stride, channels = self._color_args(pixels, on_device, stride, channels)
-        check(L().xrhip_image_upload_color(self._h, ptr, stride, channels, 1 if on_device else 0))
+        self._upload(L().xrhip_image_upload_color, pixels, on_device, stride, int(channels) if on_device else pixels.shape[2],
+                     1 if on_device else 0, interleaved=True)
 
     def upload_color_distorted(self, pixels, on_device=False, stride=None, channels=None):
         """upload_color for a frame as the camera recorded it: reduced to gray, then rectified (KltContext.set_undistort_map)."""
-        ptr, stride, channels = self._color_args(pixels, on_device, stride, channels)
-        check(L().xrhip_image_upload_color_distorted(self._h, ptr, stride, channels, 1 if on_device else 0))
-
-    def _format_args(self, pixels, on_device, stride):
-        if on_device:   # pixels: a device pointer (int) to the frame's rows
-            return C.c_void_p(int(pixels)), int(stride)
-        assert pixels.dtype == np.uint8 and pixels.ndim in (2, 3) and pixels.shape[0] == self.ctx.h, pixels.shape
-        assert pixels.strides[-1] == 1 and (pixels.ndim == 2 or pixels.strides[1] == pixels.shape[2]), pixels.strides
-        return _p(pixels), pixels.strides[0]
+        self._upload(L().xrhip_image_upload_color_distorted, pixels, on_device, stride, int(channels) if on_device else pixels.shape[2],
+                     1 if on_device else 0, interleaved=True)
 
     def upload_format(self, pixels, fmt, bits=0, limited_range=0, on_device=False, stride=None):
         """A frame in one of the XRHIP_PIXFMT_* layouts (fmt: xrslam_amd.abi.PIXFMT_*), reduced to gray on its way in: a uint8 array of the frame's
         bytes, [h][row bytes] or [h][w][bytes per pixel] (rows may be strided), or -- on_device -- a device pointer with its row
         stride in bytes."""
-        ptr, stride = self._format_args(pixels, on_device, stride)
-        check(L().xrhip_image_upload_format(self._h, ptr, stride, int(fmt), int(bits), int(limited_range), 1 if on_device else 0))
+        self._upload(L().xrhip_image_upload_format, pixels, on_device, stride, int(fmt), int(bits), int(limited_range), 1 if on_device else 0)
 
     def upload_format_distorted(self, pixels, fmt, bits=0, limited_range=0, on_device=False, stride=None):
         """upload_format for a frame as the camera recorded it: reduced to gray, then rectified (KltContext.set_undistort_map)."""
-        ptr, stride = self._format_args(pixels, on_device, stride)
-        check(L().xrhip_image_upload_format_distorted(self._h, ptr, stride, int(fmt), int(bits), int(limited_range), 1 if on_device else 0))
+        self._upload(L().xrhip_image_upload_format_distorted, pixels, on_device, stride, int(fmt), int(bits), int(limited_range),
+                     1 if on_device else 0)
 
-    def _scaled_args(self, pixels, geo, on_device, stride):
-        g = geo if isinstance(geo, FrameGeometry) else FrameGeometry(*[int(v) for v in geo])
-        if on_device:   # pixels: a device pointer (int) to row 0 of the source frame
-            return C.c_void_p(int(pixels)), int(stride), g
-        assert pixels.dtype == np.uint8 and pixels.ndim in (2, 3) and pixels.shape[0] == g.src_height, pixels.shape
-        assert pixels.strides[-1] == 1 and (pixels.ndim == 2 or pixels.strides[1] == pixels.shape[2]), pixels.strides
-        return _p(pixels), pixels.strides[0], g
-
-    def upload_scaled(self, pixels, geo, fmt=0, bits=0, limited_range=0, on_device=False, stride=None):
+    def upload_scaled(self, pixels, geo, fmt=0, bits=0, limited_range=0, on_device=False, stride=None, _fn="xrhip_image_upload_scaled"):
         """A frame larger than the context's plane, in any XRHIP_PIXFMT_* layout: the crop of `geo` = (src_width, src_height, crop_x,
         crop_y, crop_width, crop_height) is area-averaged down to the plane on its way in.  `pixels`: a uint8 array of the source
         frame's bytes, [src_height][row bytes] or [src_height][src_width][bytes per pixel] (rows may be strided), or -- on_device -- a
         device pointer to row 0 of the source frame with its row stride in bytes."""
-        ptr, stride, g = self._scaled_args(pixels, geo, on_device, stride)
-        check(L().xrhip_image_upload_scaled(self._h, ptr, stride, int(fmt), int(bits), int(limited_range), 1 if on_device else 0, C.byref(g)))
+        g = geo if isinstance(geo, FrameGeometry) else FrameGeometry(*[int(v) for v in geo])
+        self._upload(getattr(L(), _fn), pixels, on_device, stride, int(fmt), int(bits), int(limited_range), 1 if on_device else 0, C.byref(g),
+                     rows=g.src_height)
 
     def upload_scaled_distorted(self, pixels, geo, fmt=0, bits=0, limited_range=0, on_device=False, stride=None):
         """upload_scaled for a frame as the camera recorded it: scaled, then rectified (KltContext.set_undistort_map)."""
-        ptr, stride, g = self._scaled_args(pixels, geo, on_device, stride)
-        check(L().xrhip_image_upload_scaled_distorted(self._h, ptr, stride, int(fmt), int(bits), int(limited_range), 1 if on_device else 0,
-                                                      C.byref(g)))
+        self.upload_scaled(pixels, geo, fmt, bits, limited_range, on_device, stride, _fn="xrhip_image_upload_scaled_distorted")
 
     def raw(self):
         """The 8-bit frame preprocess() will read (parity aid)."""
