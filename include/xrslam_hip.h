@@ -306,6 +306,9 @@ typedef struct xrhip_ba_problem {
 #define XRHIP_BA_NO_CONVERGENCE 1
 #define XRHIP_BA_FAILURE 2
 
+/* A problem whose cost at the start is not finite (NaN or infinity in a state or an observed depth, an overflow or 0 / 0 in a factor)
+ * is refused: termination = XRHIP_BA_FAILURE, usable = 0, iterations = successful_steps = 0, and frame_state / inv_depth are left bit
+ * for bit as passed.  The call itself returns 0, and the context solves the next problem as ever. */
 typedef struct xrhip_ba_summary {
     int iterations;        /* trust-region iterations executed (successful + unsuccessful) */
     int successful_steps;

@@ -737,6 +737,13 @@ static int orc_ba_solve_impl(const xrhip_ba_problem *P, xrhip_ba_summary *summar
     std::vector<double> g;
     double x_cost = evaluate(pb, x, &H, &g);
     sm.initial_cost = x_cost;
+    if (!std::isfinite(x_cost)) {   // nothing to minimise from: FAILURE, not usable, no iteration, the caller's state bit for bit as passed
+        sm.termination = XRHIP_BA_FAILURE;
+        sm.usable = 0;
+        sm.final_cost = x_cost;
+        if (summary) *summary = sm;
+        return 0;
+    }
     // Jacobi scaling from the initial Jacobian: 1 / (1 + ||col||)
     std::vector<double> scale(n);
     for (int i = 0; i < n; ++i) scale[i] = 1.0 / (1.0 + std::sqrt(H(i, i)));

@@ -19,79 +19,12 @@ prior factor, it is run once with and once without one.  (tests/test_ba_plan_hos
   wide_trials                       ba_plan.hpp plan_solve                 M >= 256 and F <= 32
   wide_first                        ba_plan.hpp plan_solve                 wide_trials, M >= 600 and na >= 90
 """
-import numpy as np
 import pytest
 
-from tests import ba_synth as bs
+from tests.ba_hard import dims, one_free, route, subwindow, window
 from tests.ba_parity import solve_both
-from xrslam_amd import abi
 
 pytestmark = pytest.mark.gpu
-
-HELD = abi.FIX_POSE | abi.FIX_MOTION
-
-
-def _free_prior(states, frames, seed):
-    """A prior on `frames` linearised a little away from their states: diagonal sqrt-information (0.01 rad / 1 cm on the pose,
-    0.1 m/s and the biases' random walk on the motion), infovec zero."""
-    rng = np.random.RandomState(seed)
-    n = 15 * len(frames)
-    w = np.tile(np.concatenate([np.full(6, 100.0), np.full(3, 10.0), np.full(3, 1e3), np.full(3, 1e2)]), len(frames))
-    lin = states[frames].copy()
-    lin[:, 4:7] += 1e-3 * rng.randn(len(frames), 3)
-    return dict(frames=np.asarray(frames), sqrt_info=np.diag(w), infovec=np.zeros(n), lin=lin)
-
-
-def window(K, L, seed, prior, fixed=0):
-    """refine_window-shaped: free landmarks (a Schur complement), all frames free but the first `fixed`; with the window's gauge
-    prior (ba_synth.make_window) or without a prior.  na = 15 (K - fixed)."""
-    return bs.make_window(K=K, L=L, seed=seed, with_prior=prior, n_fixed_first=fixed)[0]
-
-
-def one_free(K, L, seed, prior, all_imu=False):
-    """localize_newframe-shaped: only the last frame free, every landmark held, the reprojection factors into the last frame.
-    all_imu: keep all K - 1 IMU factors (NI > 8 rules out kb_chain without a prior).  na = 15."""
-    pd, truth = bs.make_window(K=K, L=L, seed=seed, with_prior=False)
-    j = K - 1
-    fix = np.full(K, HELD, np.uint8)
-    fix[j] = 0
-    keep = pd.obs_tgt == j
-    obs = dict(tgt=pd.obs_tgt[keep], ref=pd.obs_ref[keep], lm=pd.obs_lm[keep], z_tgt=pd.obs_z_tgt[keep], z_ref=pd.obs_z_ref[keep])
-    states = truth["states"].copy()
-    states[j] = pd.frame_state[j]
-    ki = np.arange(len(pd.imu_j)) if all_imu else np.where(pd.imu_j == j)[0]
-    imu = dict(i=pd.imu_i[ki], j=pd.imu_j[ki], data=pd.imu_data[ki])
-    pr = _free_prior(states, [j], seed) if prior else None
-    return abi.BaProblemData(states, fix, bs.CAM_EXT, bs.IMU_EXT, bs.SQRT_INV_COV, truth["inv_depth"], np.ones(L, np.uint8),
-                             obs=obs, imu=imu, prior=pr, max_iterations=30)
-
-
-def subwindow(K, L, seed, prior, first_imu=True):
-    """refine_subwindow-shaped: frame 0 held, frames 1 .. K-1 free, every landmark held, only the reprojection factors of the
-    landmarks frame 0 anchors (no factor between two free poses).  first_imu=False drops the IMU factor 0 -> 1.  na = 15 (K - 1)."""
-    pd, _ = bs.make_window(K=K, L=L, seed=seed, with_prior=False, n_fixed_first=1)
-    keep = pd.obs_ref == 0
-    obs = dict(tgt=pd.obs_tgt[keep], ref=pd.obs_ref[keep], lm=pd.obs_lm[keep], z_tgt=pd.obs_z_tgt[keep], z_ref=pd.obs_z_ref[keep])
-    ki = (pd.imu_i >= 0) if first_imu else (pd.imu_i > 0)
-    imu = dict(i=pd.imu_i[ki], j=pd.imu_j[ki], data=pd.imu_data[ki])
-    pr = _free_prior(pd.frame_state, list(range(1, K)), seed) if prior else None
-    return abi.BaProblemData(pd.frame_state, pd.frame_fix, bs.CAM_EXT, bs.IMU_EXT, bs.SQRT_INV_COV, pd.inv_depth,
-                             np.ones(L, np.uint8), obs=obs, imu=imu, prior=pr, max_iterations=30)
-
-
-def dims(pd):
-    """The sizes the route decisions read: M (reprojection factors), NI, NP, na, F."""
-    free = [(f & abi.FIX_POSE) == 0 for f in pd.frame_fix], [(f & abi.FIX_MOTION) == 0 for f in pd.frame_fix]
-    na = 6 * sum(free[0]) + 9 * sum(free[1])
-    return dict(M=len(pd.obs_tgt), NI=len(pd.imu_i), NP=len(pd.prior_frames), na=na, F=len(pd.frame_state))
-
-
-def route(kind, use_lds=2, block=512, wt=0, wf=0):
-    """What xrhip_ba_debug_last_route should report (na and F are checked against the problem)."""
-    multi = kind in ("small_mid", "multi")
-    return dict(route=kind, use_lds=-1 if kind == "chain" else use_lds, sred_tiled=int(multi and use_lds == 0),
-                block=block if multi else 0, wide_trials=wt, wide_first=wf)
-
 
 # id: (problem, expected route, state rtol).  M = reprojection factors, NI = IMU factors, na = free frame dofs, F = frames.
 CASES = {

@@ -468,3 +468,44 @@ def test_overlapped_solve_cpu_shim():
         np.testing.assert_array_equal(a.inv_depth, b.inv_depth, err_msg=name)
         assert (sa.iterations, sa.termination, sa.final_cost) == (sb.iterations, sb.termination, sb.final_cost)
     ctx.close()
+
+
+# ---- a problem whose initial cost is not finite is refused: FAILURE, not usable, no iteration, the caller's arrays bit for bit as passed
+def _nonfinite_shapes():
+    from tests import ba_hard as bh
+    return {"subwindow": lambda: bh.subwindow(4, 60, 5, False), "subwindow_prior": lambda: bh.subwindow(4, 60, 5, True),
+            "one_free": lambda: bh.one_free(4, 300, 3, False), "one_free_prior": lambda: bh.one_free(4, 300, 3, True),
+            "window": lambda: bh.window(6, 80, 3, True)}
+
+
+def _poison(pd, how):
+    f = [k for k in range(len(pd.frame_state)) if (int(pd.frame_fix[k]) & 3) != 3][-1]
+    if how == "nan":
+        pd.frame_state[f, 5] = np.nan
+    elif how == "inf":
+        pd.frame_state[f, 5] = np.inf
+    elif how == "1e160":
+        pd.frame_state[f, 5] = 1e160          # finite, but the squared residuals overflow
+    else:
+        pd.inv_depth[pd.obs_lm[0]] = 0.0      # a landmark at infinity: 0 / 0 in its reprojection
+    return pd
+
+
+@pytest.mark.parametrize("how", ["nan", "inf", "1e160", "zero_depth"])
+@pytest.mark.parametrize("shape", ["subwindow", "subwindow_prior", "one_free", "one_free_prior", "window"])
+def test_nonfinite_initial_cost_is_refused(shape, how):
+    from tests import tr_model
+    pd = _poison(_nonfinite_shapes()[shape](), how)
+    a, b = pd.copy(), pd.copy()
+    sm = bo.solve(a)
+    assert not np.isfinite(sm.initial_cost)
+    assert (sm.termination, sm.usable, sm.iterations, sm.successful_steps) == (2, 0, 0, 0)   # XRHIP_BA_FAILURE
+    assert a.frame_state.tobytes() == pd.frame_state.tobytes() and a.inv_depth.tobytes() == pd.inv_depth.tobytes()
+    out = tr_model.solve(b)
+    assert not np.isfinite(out["initial_cost"])
+    assert (out["termination"], out["usable"], out["iterations"], out["successful_steps"]) == (tr_model.FAILURE, 0, 0, 0)
+    assert b.frame_state.tobytes() == pd.frame_state.tobytes() and b.inv_depth.tobytes() == pd.inv_depth.tobytes()
+    # and the next, ordinary problem solves as ever
+    good = _nonfinite_shapes()[shape]()
+    sm = bo.solve(good)
+    assert sm.usable == 1 and sm.final_cost < sm.initial_cost

@@ -243,14 +243,16 @@ class Program:
 
 def solve(pd, max_iterations=None, trace=None, refresh_bias_reference=True):
     """Runs the minimiser on an abi.BaProblemData IN PLACE (like the reference); returns a dict with iterations,
-    successful_steps, termination, initial_cost, final_cost.  trace: list receiving, per trial that reached the accept / reject
+    successful_steps, termination, usable, initial_cost, final_cost and `reason`, the test that ended the solve ("gradient", "limit",
+    "radius", "parameter", "function", "invalid", "nonfinite", or "empty" for a problem without a free block).  A problem whose initial
+    cost is not finite is refused: FAILURE, not usable, no iteration, pd untouched.  trace: list receiving, per trial that reached the accept / reject
     decision, (iteration, x_cost, candidate_cost, model_cost_change, relative_decrease, radius, step_norm, mu, accepted).
     refresh_bias_reference=False: the IMU factors keep the bias reference of the solve's start (NOT the reference's behaviour;
     tests use it to show what the refresh does)."""
     prog = Program(pd)
     max_it = int(pd.max_iterations if max_iterations is None else max_iterations)
     x_states, x_depths = np.array(pd.frame_state), np.array(pd.inv_depth)
-    out = dict(iterations=0, successful_steps=0, termination=CONVERGENCE)
+    out = dict(iterations=0, successful_steps=0, termination=CONVERGENCE, usable=1, reason="empty")
     if prog.n == 0:
         out.update(initial_cost=0.0, final_cost=0.0)
         return out
@@ -261,6 +263,9 @@ def solve(pd, max_iterations=None, trace=None, refresh_bias_reference=True):
     x_cost, g, H = prog.evaluate(x_states, x_depths, bias_ref, True)
     scale = 1.0 / (1.0 + np.sqrt(np.diag(H)))
     out["initial_cost"] = x_cost
+    if not np.isfinite(x_cost):                             # nothing to minimise from: the caller's state is left as it was passed
+        out.update(termination=FAILURE, usable=0, final_cost=x_cost, reason="nonfinite")
+        return out
 
     def gradient_max_norm(S, D, grad):
         S2, D2 = prog.apply(S, D, -grad)
@@ -272,25 +277,25 @@ def solve(pd, max_iterations=None, trace=None, refresh_bias_reference=True):
     iteration, invalid, last_successful = 0, 0, True        # iteration 0 counts as successful for the gradient test
     dl = {}                                                  # what DoglegStrategy keeps between calls while reuse is set
 
-    def finish(term):
+    def finish(term, reason):
         pd.frame_state[:] = x_states
         pd.inv_depth[:] = x_depths
-        out.update(iterations=iteration, termination=term, final_cost=x_cost)
+        out.update(iterations=iteration, termination=term, usable=int(term != FAILURE), final_cost=x_cost, reason=reason)
         return out
 
     if gmax <= GRADIENT_TOLERANCE:
-        return finish(CONVERGENCE)
+        return finish(CONVERGENCE, "gradient")
     while True:
         # ---- FinalizeIterationAndCheckIfMinimizerCanContinue (callbacks first: the state-updating one refreshes the user state
         # -- hence the IMU factors' bias reference -- after a successful iteration)
         if last_successful and refresh_bias_reference:
             bias_ref = user_bias(x_states)
         if iteration >= max_it:
-            return finish(NO_CONVERGENCE)
+            return finish(NO_CONVERGENCE, "limit")
         if last_successful and gmax <= GRADIENT_TOLERANCE:
-            return finish(CONVERGENCE)
+            return finish(CONVERGENCE, "gradient")
         if radius < MIN_RADIUS:
-            return finish(CONVERGENCE)
+            return finish(CONVERGENCE, "radius")
         iteration += 1
         # ---- DoglegStrategy::ComputeStep on the column-scaled Jacobian: Hs = S H S, gs = S g
         if not reuse:
@@ -338,7 +343,7 @@ def solve(pd, max_iterations=None, trace=None, refresh_bias_reference=True):
         if not valid:
             invalid += 1
             if invalid >= MAX_CONSECUTIVE_INVALID_STEPS:
-                return finish(FAILURE)
+                return finish(FAILURE, "invalid")
             mu *= MU_INCREASE                               # DoglegStrategy::StepIsInvalid
             reuse = False
             last_successful = False
@@ -347,12 +352,14 @@ def solve(pd, max_iterations=None, trace=None, refresh_bias_reference=True):
         delta = step * scale                                # back to the unscaled local coordinates
         c_states, c_depths = prog.apply(x_states, x_depths, delta)
         cand_cost, _, _ = prog.evaluate(c_states, c_depths, bias_ref, False)
+        if not np.isfinite(cand_cost):
+            cand_cost = np.finfo(float).max                 # a candidate that cannot be evaluated is a very bad one: rejected
         # ---- ParameterToleranceReached / FunctionToleranceReached
         step_norm = float(np.linalg.norm(prog.ambient(x_states, x_depths) - prog.ambient(c_states, c_depths)))
         if step_norm <= PARAMETER_TOLERANCE * (x_norm + PARAMETER_TOLERANCE):
-            return finish(CONVERGENCE)
+            return finish(CONVERGENCE, "parameter")
         if abs(x_cost - cand_cost) <= FUNCTION_TOLERANCE * x_cost:
-            return finish(CONVERGENCE)
+            return finish(CONVERGENCE, "function")
         rel = (x_cost - cand_cost) / model_change
         accepted = rel > MIN_RELATIVE_DECREASE
         if trace is not None:

@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <vector>
 
 using namespace xrhip;
@@ -924,6 +925,22 @@ static bool any_free_block(const xrhip_ba_problem *P) {
         if ((P->frame_fix[f] & 3) != 3) return true;
     return false;
 }
+// A NaN or an infinity in a frame's state, or in the inverse depth of a landmark some observation names: the cost of such a problem is
+// not finite and there is nothing to minimise from.  xrhip_ba_solve refuses it before anything is staged or launched (FAILURE, not
+// usable, no iteration, the caller's arrays untouched).  One pass over 16 F + M doubles.
+static bool inputs_finite(const xrhip_ba_problem *P) {
+    bool ok = true;
+    for (int i = 0; i < 16 * P->n_frames; ++i) ok &= std::isfinite(P->frame_state[i]);
+    for (int o = 0; o < P->n_obs; ++o) ok &= std::isfinite(P->inv_depth[P->obs_lm[o]]);
+    return ok;
+}
+static void refuse_summary(xrhip_ba_summary *sm) {
+    if (!sm) return;
+    std::memset(sm, 0, sizeof(*sm));
+    sm->termination = XRHIP_BA_FAILURE;
+    sm->usable = 0;
+    sm->initial_cost = sm->final_cost = std::numeric_limits<double>::quiet_NaN();
+}
 static void fill_summary(const BaCtl &ctl, float ms, xrhip_ba_summary *sm) {
     if (!sm) return;
     std::memset(sm, 0, sizeof(*sm));
@@ -1042,7 +1059,8 @@ int xrhip_ba_solve_begin(xrhip_ba *c, const xrhip_ba_problem *P) {
     // queue for two kernels (216 us) while the next batch waits -- two single batches with the host round trip in between serve
     // ten sequences better (5718 -> 5861 frames/s, profiles/r04_multi_sequence.md).  The caller falls back to xrhip_ba_solve.
     const BaSwitches &sw = ba_switches();
-    if (sw.no_chained_solves || (c->group && !sw.group_chained_solves) || c->preint_deferred || !any_free_block(P)) return 0;
+    if (sw.no_chained_solves || (c->group && !sw.group_chained_solves) || c->preint_deferred || !any_free_block(P) || !inputs_finite(P))
+        return 0;   // (xrhip_ba_solve refuses a non-finite problem)
     xrhip_ba::Begun &B = c->begun;
     B.t0 = std::chrono::steady_clock::now();
     Ext cam, imu;
@@ -1098,7 +1116,7 @@ int xrhip_ba_solve_linked(xrhip_ba *c2, const xrhip_ba_problem *P2, xrhip_ba_sum
         std::memcpy(P2->frame_state + 16 * (size_t)link_second, c1->h_out + 16 * (size_t)link_first, sizeof(double) * 16);
         return xrhip_ba_solve_overlapped(c2, P2, s2, host_work, arg);
     };
-    if (c1->group != c2->group || c2->begun.active || !any_free_block(P2)) return sequential();
+    if (c1->group != c2->group || c2->begun.active || !any_free_block(P2) || !inputs_finite(P2)) return sequential();   // (refused there)
     const auto t_begin = std::chrono::steady_clock::now();   // the first solve's clock stops here ONCE the linked request is out (below)
     BaDims d2;
     SolvePlan pl2;
@@ -1164,6 +1182,10 @@ static int ba_solve_impl(xrhip_ba *c, const xrhip_ba_problem *P, xrhip_ba_summar
             summary->termination = XRHIP_BA_CONVERGENCE;
             summary->usable = 1;
         }
+        return preint_launch_deferred(c, P, nullptr);
+    }
+    if (!inputs_finite(P)) {
+        refuse_summary(summary);
         return preint_launch_deferred(c, P, nullptr);
     }
     BaDims d;

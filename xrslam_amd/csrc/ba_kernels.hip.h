@@ -1527,7 +1527,12 @@ __device__ __forceinline__ void trial_store(BaCtl *c, const TrialScalars &t) {  
 // FinalizeIterationAndCheckIfMinimizerCanContinue + start of the next iteration, for the first trial of a launch
 __device__ __forceinline__ void trial_begin(TrialScalars &t, bool skip_finalize, bool check_gradient) {
     if (!skip_finalize) {
-        if (t.iteration >= t.max_iterations) {
+        if (check_gradient && t.iteration == 0 && !isfinite(t.x_cost)) {
+            // the cost at the start is not finite (an overflow, 0 / 0 in a factor): nothing to minimise from.  No iteration, no step:
+            // the states go back as they came (xrslam_hip.h, xrhip_ba_summary)
+            t.termination = XRHIP_BA_FAILURE;
+            t.status = ST_DONE;
+        } else if (t.iteration >= t.max_iterations) {
             t.termination = XRHIP_BA_NO_CONVERGENCE;
             t.status = ST_DONE;
         } else if (check_gradient && t.gmax <= TR_GRADIENT_TOLERANCE) {
