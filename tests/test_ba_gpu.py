@@ -309,7 +309,10 @@ def _marg_problem(pd, victim=0):
                                pd.inv_depth, obs)
 
 
-def _marg_parity(ctx, bo, md, tag):
+def _marg_parity(ctx, bo, md, tag, family):
+    """family: "first" (the window's gauge prior: rank deficient) or "chained" (on top of a marginalisation's prior) -- the tolerance
+    of tests/marg_metric.py the scale-aware comparison is held to, after the max-norm one"""
+    from tests import marg_metric
     si_o, iv_o, lin_o = bo.marginalize(md)
     si_h, iv_h, lin_h = ctx.marginalize(md)
     Lo, Lh = si_o.T @ si_o, si_h.T @ si_h
@@ -320,6 +323,13 @@ def _marg_parity(ctx, bo, md, tag):
     assert np.abs(Lh - Lo).max() <= 1e-8 * np.abs(Lo).max()
     assert np.abs(eh - eo).max() <= 1e-7 * max(1.0, np.abs(eo).max())
     np.testing.assert_array_equal(lin_h, lin_o)
+    try:
+        dev = marg_metric.check_priors(si_h, iv_h, si_o, iv_o, family, tag)
+    except AssertionError:
+        _dump("marg_scaled_mismatch_" + tag, Lo=Lo, Lh=Lh, eo=eo, eh=eh, ivo=iv_o)
+        raise
+    print("marg %-18s %-7s path %d  support %3d of %3d  dLambda %.2e  deta %.2e" % (
+        tag, family, ctx.marg_guard()[1][4], len(dev["sup"]), len(Lo), dev["dlam"], dev["deta"]))
     return si_h, iv_h, lin_h
 
 
@@ -331,7 +341,7 @@ def test_marginalization_parity(ctx, bo, K, Ln, seed):
     pd, _ = bs.make_window(K=K, L=Ln, seed=seed)
     pd.frame_state[1:, 4:7] += 1e-3
     md = _marg_problem(pd, 0)
-    si_h, iv_h, lin_h = _marg_parity(ctx, bo, md, "%d" % seed)
+    si_h, iv_h, lin_h = _marg_parity(ctx, bo, md, "%d" % seed, "first")
     paths = [ctx.marg_guard()[1]]
     # second marginalisation on top of the first (prior with a dense sqrt_info), via a solve in between
     p2 = _next_window(pd, si_h, iv_h, lin_h)
@@ -339,7 +349,7 @@ def test_marginalization_parity(ctx, bo, K, Ln, seed):
     # and the marginalisations that follow, each on top of the prior the one before produced
     cur = p2
     for step in range(1, 4):
-        si_h, iv_h, lin_h = _marg_parity(ctx, bo, _marg_problem(cur, 0), "%d_step%d" % (seed, step))
+        si_h, iv_h, lin_h = _marg_parity(ctx, bo, _marg_problem(cur, 0), "%d_step%d" % (seed, step), "chained")
         paths.append(ctx.marg_guard()[1])
         if paths[-1][4] == 0:
             break
@@ -380,7 +390,7 @@ def test_marginalization_past_its_size_limit_is_refused(ctx, bo):
     pd, _ = bs.make_window(K=11, L=150, seed=21)
     pd.frame_state[1:, 4:7] += 1e-3
     _solve_both(ctx, bo, pd, "after_refused_marg")
-    _marg_parity(ctx, bo, _marg_problem(pd, 0), "after_refused")
+    _marg_parity(ctx, bo, _marg_problem(pd, 0), "after_refused", "first")
 
 
 def test_marginalization_begin_end_equals_the_blocking_call(ctx):

@@ -3,7 +3,10 @@
 // Enabled by the environment:  XRSLAM_AMD_DUMP_BA=<directory>  [XRSLAM_AMD_DUMP_MIN_OBS=<n>]  [XRSLAM_AMD_DUMP_EVERY=<k>]
 // File layout (little endian): "XRBA1\0\0\0", 8 int32 counts {F, L, M, MR, NI, NP, max_iterations, 0}, then the arrays
 // of xrhip_ba_problem in declaration order (include/xrslam_hip.h), doubles as f64, indices as i32, flags as u8.
-// tests/ba_snapshots.py reads it back.  No HIP dependency.
+// The same directory receives the problems handed to xrhip_ba_marginalize (Pipeline's marginalize_frame), every one of them
+// (the two filters above are the solves'): "XRMG1\0\0\0", 8 int32 counts {F, victim, NP, NI, L, M, 0, 0}, then the arrays of
+// xrhip_marg_problem in declaration order (tests/golden/ba_snapshots/marg_*.npz are made from these files).
+// tests/ba_snapshots.py reads both back.  No HIP dependency.
 #pragma once
 #include <mutex>
 #include <algorithm>
@@ -57,6 +60,32 @@ struct BaDumper {
         wd(pb.imu_data, (size_t)XRHIP_IMU_DIM * NI);
         wi(pb.prior_frames, NP);
         wd(pb.prior_sqrt_info, 225 * NP * NP); wd(pb.prior_infovec, 15 * NP); wd(pb.prior_lin, 16 * NP);
+        std::fclose(fp);
+    }
+    long marg_written = 0;
+    void dump_marg(const xrhip_marg_problem &mp, long frame_count) {
+        if (!enabled()) return;
+        char name[512];
+        std::snprintf(name, sizeof name, "%s/marg_%05ld_f%05ld_F%d_L%d_M%d.xrmg", dir.c_str(), marg_written++, frame_count, mp.n_frames,
+                      mp.n_landmarks, mp.n_obs);
+        FILE *fp = std::fopen(name, "wb");
+        if (!fp) return;
+        const char magic[8] = {'X', 'R', 'M', 'G', '1', 0, 0, 0};
+        const int32_t hdr[8] = {mp.n_frames, mp.victim, mp.prior_n, mp.n_imu, mp.n_landmarks, mp.n_obs, 0, 0};
+        std::fwrite(magic, 1, 8, fp);
+        std::fwrite(hdr, sizeof(int32_t), 8, fp);
+        auto wd = [&](const double *p, size_t n) { if (n) std::fwrite(p, sizeof(double), n, fp); };
+        auto wi = [&](const int *p, size_t n) { if (n) std::fwrite(p, sizeof(int), n, fp); };
+        const size_t F = mp.n_frames, NP = mp.prior_n, NI = mp.n_imu, L = mp.n_landmarks, M = mp.n_obs;
+        wd(mp.frame_state, 16 * F);
+        wd(mp.cam_q_bc, 4); wd(mp.cam_p_bc, 3); wd(mp.imu_q_bi, 4); wd(mp.imu_p_bi, 3); wd(mp.sqrt_inv_cov, 2);
+        wi(mp.prior_frames, NP);
+        wd(mp.prior_sqrt_info, 225 * NP * NP); wd(mp.prior_infovec, 15 * NP); wd(mp.prior_lin, 16 * NP);
+        wi(mp.imu_i, NI); wi(mp.imu_j, NI);
+        wd(mp.imu_data, (size_t)XRHIP_IMU_DIM * NI);
+        wd(mp.inv_depth, L);
+        wi(mp.obs_tgt, M); wi(mp.obs_ref, M); wi(mp.obs_lm, M);
+        wd(mp.obs_z_tgt, 3 * M); wd(mp.obs_z_ref, 3 * M);
         std::fclose(fp);
     }
 };

@@ -1212,6 +1212,7 @@ inline void marginalize_frame(Pipeline &P, Map *map, size_t index) {   // Map::m
     mp.obs_lm = ol.data();
     mp.obs_z_tgt = zt.data();
     mp.obs_z_ref = zr.data();
+    if (P.ba_dump.enabled()) P.ba_dump.dump_marg(mp, P.times.frames);
     {   // queued on the marginalisation's own context; the new sqrt_info / infovec / lin are fetched on first use
         WallTimer wt_w_marginalize(P.times.w_marginalize);
         static const bool sync_launch = std::getenv("XRSLAM_AMD_SYNC_MARG_LAUNCH") != nullptr;   // development switch
