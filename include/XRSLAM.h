@@ -223,6 +223,23 @@ void XRSLAMAmdGetCameraConfig(XRSLAMAmdCameraConfig *out);
  * ...): lets a caller -- and tests/test_config.py -- check that two sets of files mean the same configuration.  Writes at most cap - 1
  * characters plus the terminator; returns the length the full text needs. */
 int XRSLAMAmdDescribeConfig(char *buf, int cap);
+/* Lucas-Kanade parameters of the tracker.  The reference hard-codes them in OpenCvImage::track_keypoints (winSize 21 x 21, maxLevel 3,
+ * 30 iterations, epsilon 0.01: opencv_image.cpp:96-99), tuned for roughly VGA frames.  Four OPTIONAL keys of the slam yaml -- extensions,
+ * the reference's files do not have them and load as before; an absent key means the reference's constant:
+ *   feature_tracker.lk_window_size     odd, 5..21
+ *   feature_tracker.lk_max_level       0..5; level lk_max_level of the working image (each level (n + 1) / 2) must be larger than the
+ *                                      window in both dimensions
+ *   feature_tracker.lk_max_iterations  1..100
+ *   feature_tracker.lk_epsilon         0..10
+ * A value outside these rules makes XRSLAMCreate / XRSLAMAmdInstanceCreate fail with the reason in XRSLAMAmdLastError.  Values other
+ * than the reference's run the tracker's kernels with runtime parameters (xrslam_hip.h: xrhip_klt_set_lk_params) and such an instance
+ * cannot join a group (XRSLAMAmdInstanceJoinGroup fails).  XRSLAMAmdDescribeConfig prints the four keys only for a file that has one
+ * of them.  Returns 1 with the values in use, 0 when there is no instance. */
+typedef struct XRSLAMAmdTrackerParams {
+    int lk_window_size, lk_max_level, lk_max_iterations;
+    double lk_epsilon;
+} XRSLAMAmdTrackerParams;
+int XRSLAMAmdGetTrackerParams(XRSLAMAmdTrackerParams *out);
 /* Undistortion on the device.  The reference's readers rectify every frame on the host before pushing it
  * (cv::undistort, xrslam-pc/player/src/IO/euroc_dataset_reader.cpp:62-69; xrslam::extra::ImageUndistorter,
  * IO/tum_dataset_reader.cpp:67-76).  After this call the images handed to XRSLAM_SENSOR_CAMERA / XRSLAMAmdPushImageDevice
@@ -346,6 +363,7 @@ void XRSLAMAmdInstanceGetTimes(XRSLAMAmdInstance *inst, XRSLAMAmdTimes *out);
 void XRSLAMAmdInstanceSetProfiling(XRSLAMAmdInstance *inst, int enable);
 void XRSLAMAmdInstanceGetBaStats(XRSLAMAmdInstance *inst, void *xrhip_ba_stats_out, int reset);
 void XRSLAMAmdInstanceGetKltStats(XRSLAMAmdInstance *inst, void *xrhip_klt_stats_out, int reset);
+int XRSLAMAmdInstanceGetTrackerParams(XRSLAMAmdInstance *inst, XRSLAMAmdTrackerParams *out);
 void XRSLAMAmdInstanceGetInitReport(XRSLAMAmdInstance *inst, XRSLAMAmdInitReport *out);
 const char *XRSLAMAmdInstanceLastError(XRSLAMAmdInstance *inst);
 void XRSLAMAmdInstanceSetThreading(XRSLAMAmdInstance *inst, int mode);

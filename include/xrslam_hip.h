@@ -244,6 +244,26 @@ typedef struct xrhip_klt_stats {
     long long lk_points;       /* points submitted to track */
     long long detect_full_list;   /* detections that fell back from the strongest-candidate block to the full list */
 } xrhip_klt_stats;
+/* Lucas-Kanade parameters of a context: cv::calcOpticalFlowPyrLK's winSize (square), maxLevel and criteria (COUNT + EPS).
+ *   win        odd, 5..21 (the planes keep their 21-pixel border; larger windows are not supported)
+ *   max_level  0..5; the pyramid has max_level + 1 levels of size (n + 1) / 2 each.  Level max_level must be larger than win in both
+ *              dimensions -- cv::buildOpticalFlowPyramid's stopping rule, here an argument check, not a silent clamp.  (The reference's
+ *              own pair 21 / 3 is accepted at any frame size, as it always was.)
+ *   max_count  1..100 iterations per level
+ *   epsilon    0..10; a level stops when (double)dx*dx + (double)dy*dy <= epsilon*epsilon
+ * NULL = the reference's 21 / 3 / 30 / 0.01 (opencv_image.cpp:96-99), which is what a new context has.  Anything outside the ranges:
+ * XRHIP_EINVAL, the message names the field, the context is unchanged.  XRHIP_ESTATE when the context already has images (their
+ * pyramid storage is sized by max_level: set the parameters right after xrhip_klt_create) or is a member of a group.
+ * At the reference's values the kernels specialised on them run, exactly as before.  With any other value the kernels with runtime
+ * parameters run: same arithmetic, same order of decisions, bit-identical to oracle/klt_oracle.c's orc_lk at those parameters; the gates
+ * of xrhip_image_track (20-pixel border, displacement <= rows / 4, forward-backward <= 0.5) do not change.  Such a context cannot join
+ * a group (xrhip_klt_join_group: XRHIP_ESTATE): the group's shared launches are the specialised kernels.
+ * xrhip_debug_force_general_lk (parity / measurement aid): on = 1 runs the kernels with runtime parameters at ANY values, the
+ * reference's included; XRHIP_ESTATE for a member of a group. */
+typedef struct xrhip_lk_params { int win; int max_level; int max_count; double epsilon; } xrhip_lk_params;
+int xrhip_klt_set_lk_params(xrhip_klt *ctx, const xrhip_lk_params *p);
+int xrhip_klt_get_lk_params(const xrhip_klt *ctx, xrhip_lk_params *out);
+int xrhip_debug_force_general_lk(xrhip_klt *ctx, int on);
 int xrhip_klt_set_profiling(xrhip_klt *ctx, int enable);
 int xrhip_klt_get_stats(xrhip_klt *ctx, xrhip_klt_stats *out, int reset);
 int xrhip_klt_synchronize(xrhip_klt *ctx);

@@ -44,6 +44,11 @@ struct Config {
     double feature_tracker_clahe_clip_limit = 6.0;
     size_t feature_tracker_clahe_width = 8, feature_tracker_clahe_height = 8;
     bool feature_tracker_predict_keypoints = true;
+    // Lucas-Kanade parameters: extensions (the reference hard-codes them, opencv_image.cpp:96-99; its files do not have the keys).
+    // Absent keys = the reference's constants; feature_tracker_lk_keys = at least one of the four was present in the file.
+    double feature_tracker_lk_window_size = 21, feature_tracker_lk_max_level = 3, feature_tracker_lk_max_iterations = 30;
+    double feature_tracker_lk_epsilon = 0.01;
+    bool feature_tracker_lk_keys = false;
     size_t initializer_keyframe_num = 8, initializer_keyframe_gap = 5, initializer_min_matches = 50;
     double initializer_min_parallax = 10;
     size_t initializer_min_triangulation = 50, initializer_min_landmarks = 30;
@@ -201,6 +206,13 @@ inline Config load_config(const std::string &slam_path, const std::string &devic
     siz("feature_tracker.clahe_width", c.feature_tracker_clahe_width);
     siz("feature_tracker.clahe_height", c.feature_tracker_clahe_height);
     boo("feature_tracker.predict_keypoints", c.feature_tracker_predict_keypoints);
+    // (kept as the numbers the file holds: a fractional window or a negative level is refused where the values are checked, not rounded here)
+    num("feature_tracker.lk_window_size", c.feature_tracker_lk_window_size);
+    num("feature_tracker.lk_max_level", c.feature_tracker_lk_max_level);
+    num("feature_tracker.lk_max_iterations", c.feature_tracker_lk_max_iterations);
+    num("feature_tracker.lk_epsilon", c.feature_tracker_lk_epsilon);
+    c.feature_tracker_lk_keys = slam.count("feature_tracker.lk_window_size") || slam.count("feature_tracker.lk_max_level") ||
+                                slam.count("feature_tracker.lk_max_iterations") || slam.count("feature_tracker.lk_epsilon");
     siz("initializer.keyframe_num", c.initializer_keyframe_num);
     siz("initializer.keyframe_gap", c.initializer_keyframe_gap);
     siz("initializer.min_matches", c.initializer_min_matches);
@@ -270,6 +282,12 @@ inline std::string describe_config(const Config &c) {
     put("feature_tracker.clahe_width", {(double)c.feature_tracker_clahe_width});
     put("feature_tracker.clahe_height", {(double)c.feature_tracker_clahe_height});
     put("feature_tracker.predict_keypoints", {c.feature_tracker_predict_keypoints ? 1.0 : 0.0});
+    if (c.feature_tracker_lk_keys) {   // extensions: printed only for a file that has them, the output for the reference's files is unchanged
+        put("feature_tracker.lk_window_size", {c.feature_tracker_lk_window_size});
+        put("feature_tracker.lk_max_level", {c.feature_tracker_lk_max_level});
+        put("feature_tracker.lk_max_iterations", {c.feature_tracker_lk_max_iterations});
+        put("feature_tracker.lk_epsilon", {c.feature_tracker_lk_epsilon});
+    }
     put("initializer.keyframe_num", {(double)c.initializer_keyframe_num});
     put("initializer.keyframe_gap", {(double)c.initializer_keyframe_gap});
     put("initializer.min_matches", {(double)c.initializer_min_matches});

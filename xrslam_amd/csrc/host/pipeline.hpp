@@ -61,6 +61,9 @@ int xrhip_image_upload_scaled_distorted(xrhip_image *img, const void *pixels, in
 // (likewise the tracking view's renderer: the feature snapshot below needs nothing of it)
 int xrhip_image_render_view(xrhip_image *img, const xrhip_view_segment *segs, int n_segs, const xrhip_view_marker *markers, int n_markers,
                             const uint8_t *palette_bgr, int n_palette, void *out, int stride_bytes, int channels, int on_device) __attribute__((weak));
+// (likewise the Lucas-Kanade parameters: a library without the entry point tracks with the reference's constants, which is all the
+// configuration may then ask for -- Pipeline::apply_lk_params)
+int xrhip_klt_set_lk_params(xrhip_klt *ctx, const xrhip_lk_params *p) __attribute__((weak));
 }
 
 namespace xrh {
@@ -246,10 +249,61 @@ struct Pipeline {
     InitLogger init_log;               // XRSLAM_AMD_DUMP_INIT=<file>: decisions of the initialiser and of the RD-VIO filters with their inputs (ba_dump.hpp)
     OutLogger out_log;                 // XRSLAM_AMD_DUMP_OUT=<file>: what every frame produces -- key points, track ids, states, landmarks (ba_dump.hpp)
 
+    // feature_tracker.lk_* (extensions, config.hpp): checked here, so that a bad value fails the creation with a message that names
+    // the key whatever library lies behind xrslam_hip.h; the rules are xrhip_klt_set_lk_params' (include/xrslam_hip.h).
+    // -> true when the values are not the reference's 21 / 3 / 30 / 0.01
+    static bool check_lk_params(const Config &c, xrhip_lk_params &p) {
+        auto whole = [](double v, double lo, double hi) { return v >= lo && v <= hi && v == (double)(long long)v; };
+        const double win = c.feature_tracker_lk_window_size, lev = c.feature_tracker_lk_max_level, cnt = c.feature_tracker_lk_max_iterations,
+                     eps = c.feature_tracker_lk_epsilon;
+        char b[256];
+        if (!whole(win, 5, 21) || (long long)win % 2 == 0) {
+            std::snprintf(b, sizeof b, "config: feature_tracker.lk_window_size = %g: an odd whole number, 5..21", win);
+            throw ConfigError(b);
+        }
+        if (!whole(lev, 0, 5)) {
+            std::snprintf(b, sizeof b, "config: feature_tracker.lk_max_level = %g: a whole number, 0..5", lev);
+            throw ConfigError(b);
+        }
+        if (!whole(cnt, 1, 100)) {
+            std::snprintf(b, sizeof b, "config: feature_tracker.lk_max_iterations = %g: a whole number, 1..100", cnt);
+            throw ConfigError(b);
+        }
+        if (!(eps >= 0.0 && eps <= 10.0)) {
+            std::snprintf(b, sizeof b, "config: feature_tracker.lk_epsilon = %g: 0..10", eps);
+            throw ConfigError(b);
+        }
+        p = xrhip_lk_params{(int)win, (int)lev, (int)cnt, eps};
+        const bool reference = p.win == 21 && p.max_level == 3 && p.max_count == 30 && p.epsilon == 0.01;
+        if (!(p.win == 21 && p.max_level == 3)) {
+            int tw = (int)c.cam_resolution[0], th = (int)c.cam_resolution[1];
+            for (int l = 0; l < p.max_level; ++l) {
+                tw = (tw + 1) / 2;
+                th = (th + 1) / 2;
+            }
+            if (tw <= p.win || th <= p.win) {
+                std::snprintf(b, sizeof b, "config: feature_tracker.lk_max_level = %d: level %d of a %d x %d frame is %d x %d, not larger than lk_window_size = %d",
+                              p.max_level, p.max_level, (int)c.cam_resolution[0], (int)c.cam_resolution[1], tw, th, p.win);
+                throw ConfigError(b);
+            }
+        }
+        return !reference;
+    }
     explicit Pipeline(const Config &c) : config(c) {
+        xrhip_lk_params lk;
+        const bool lk_set = check_lk_params(c, lk);
+        if (lk_set && !xrhip_klt_set_lk_params)
+            throw ConfigError("config: feature_tracker.lk_* other than the reference's 21 / 3 / 30 / 0.01 need a library with xrhip_klt_set_lk_params; "
+                              "this one tracks with the reference's constants only");
         hip_check(xrhip_klt_create((int)c.cam_resolution[0], (int)c.cam_resolution[1],
                                    (int)c.feature_tracker_max_keypoint_detection, &klt),
                   "xrhip_klt_create");
+        if (lk_set && xrhip_klt_set_lk_params(klt, &lk) != 0) {   // (before the first image; at the reference's values no call: nothing changes)
+            const std::string why = std::string("xrhip_klt_set_lk_params: ") + xrhip_last_error();
+            xrhip_klt_destroy(klt);
+            klt = nullptr;
+            throw std::runtime_error(why);
+        }
         hip_check(xrhip_ba_create(32, 2048, 16384, &ba), "xrhip_ba_create");
         hip_check(xrhip_ba_create(32, 2048, 16384, &ba_marg), "xrhip_ba_create");
         hip_check(xrhip_ba_create(32, 2048, 16384, &ba_aux), "xrhip_ba_create");

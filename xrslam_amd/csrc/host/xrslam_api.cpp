@@ -439,6 +439,16 @@ int impl_render_view(Manager &m, void *out, int stride, int channels, int on_dev
     }
 }
 
+int impl_get_tracker_params(Manager &m, XRSLAMAmdTrackerParams *out) {
+    if (!m.sys || !out) return 0;
+    const xrh::Config &c = m.sys->P.config;   // (checked whole numbers: Pipeline::check_lk_params)
+    out->lk_window_size = (int)c.feature_tracker_lk_window_size;
+    out->lk_max_level = (int)c.feature_tracker_lk_max_level;
+    out->lk_max_iterations = (int)c.feature_tracker_lk_max_iterations;
+    out->lk_epsilon = c.feature_tracker_lk_epsilon;
+    return 1;
+}
+
 void impl_get_init_report(Manager &m, XRSLAMAmdInitReport *out) {
     if (!m.sys || !out) return;
     const xrh::Initializer &in = m.sys->init;
@@ -507,6 +517,7 @@ void XRSLAMAmdSetProfiling(int enable) { impl_set_profiling(mgr(), enable); }
 void XRSLAMAmdGetBaStats(void *out, int reset) { impl_get_ba_stats(mgr(), out, reset); }
 void XRSLAMAmdGetKltStats(void *out, int reset) { impl_get_klt_stats(mgr(), out, reset); }
 void XRSLAMAmdGetInitReport(XRSLAMAmdInitReport *out) { impl_get_init_report(mgr(), out); }
+int XRSLAMAmdGetTrackerParams(XRSLAMAmdTrackerParams *out) { return impl_get_tracker_params(mgr(), out); }
 const char *XRSLAMAmdLastError(void) { return mgr().last_error.c_str(); }
 void XRSLAMAmdSetThreading(int mode) { impl_set_threading(mgr(), mode); }
 void XRSLAMAmdFlush(void) { impl_flush(mgr()); }
@@ -588,6 +599,9 @@ void XRSLAMAmdInstanceGetKltStats(XRSLAMAmdInstance *inst, void *out, int reset)
 }
 void XRSLAMAmdInstanceGetInitReport(XRSLAMAmdInstance *inst, XRSLAMAmdInitReport *out) {
     if (inst) impl_get_init_report(inst->m, out);
+}
+int XRSLAMAmdInstanceGetTrackerParams(XRSLAMAmdInstance *inst, XRSLAMAmdTrackerParams *out) {
+    return inst ? impl_get_tracker_params(inst->m, out) : 0;
 }
 const char *XRSLAMAmdInstanceLastError(XRSLAMAmdInstance *inst) { return inst ? inst->m.last_error.c_str() : ""; }
 void XRSLAMAmdInstanceSetThreading(XRSLAMAmdInstance *inst, int mode) {

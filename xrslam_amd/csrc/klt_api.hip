@@ -139,6 +139,10 @@ struct xrhip_klt {
     uint8_t *scale_src = nullptr;
     size_t scale_cap = 0;
     hipEvent_t span_t0 = nullptr, span_t1 = nullptr;   // xrhip_debug_stream_span
+    // LK parameters (xrhip_klt_set_lk_params): at the reference's values, with the switch off, the specialised kernels run
+    xrhip_lk_params lk{XRHIP_KLT_WIN, XRHIP_KLT_LEVELS - 1, 30, 0.01};
+    bool force_general = false;   // xrhip_debug_force_general_lk
+    int n_images = 0;             // images alive: their pyramid storage is sized by lk.max_level
 };
 
 struct xrhip_image {
@@ -148,7 +152,8 @@ struct xrhip_image {
     bool have_pyramid = false;
     bool want_detect = false;   // xrhip_image_prefetch_detect: queue the Harris pass behind the next tracking launch
     int detect_seq = 0;         // != 0: the Harris pass of this image is in flight / done under that sequence number
-    LevelBuf lv[KLT_LEVELS];
+    int levels = KLT_LEVELS;    // ctx->lk.max_level + 1 when the image was created
+    LevelBuf lv[KLT_MAX_LEVELS];
 };
 
 static PyrView make_view(const xrhip_image *img) {
@@ -162,6 +167,28 @@ static PyrView make_view(const xrhip_image *img) {
         v.lv[l].pstride = img->lv[l].istride;
     }
     return v;
+}
+
+static bool lk_is_default(const xrhip_lk_params &p) {
+    return p.win == XRHIP_KLT_WIN && p.max_level == XRHIP_KLT_LEVELS - 1 && p.max_count == 30 && p.epsilon == 0.01;
+}
+// the kernels with runtime parameters run for this context (klt_kernels.hip.h, "LK with runtime parameters")
+static bool lk_general(const xrhip_klt *c) { return c->force_general || !lk_is_default(c->lk); }
+static PyrViewG make_view_g(const xrhip_image *img) {
+    PyrViewG v;
+    std::memset(&v, 0, sizeof(v));
+    for (int l = 0; l < img->levels; ++l) {
+        v.lv[l].img = img->lv[l].img;
+        v.lv[l].der = img->lv[l].der;
+        v.lv[l].w = img->lv[l].w;
+        v.lv[l].h = img->lv[l].h;
+        v.lv[l].istride = img->lv[l].istride;
+        v.lv[l].pstride = img->lv[l].istride;
+    }
+    return v;
+}
+static LkParams lk_device_params(const xrhip_klt *c) {
+    return LkParams{c->lk.win, c->lk.max_level + 1, c->lk.max_count, c->lk.epsilon * c->lk.epsilon};
 }
 
 static int ensure_points(xrhip_klt *c, int n) {
@@ -437,6 +464,8 @@ int xrhip_klt_join_group(xrhip_klt *c, xrhip_group *g) {
     if (c->group == g) return XRHIP_OK;
     if (g && group_device(g) != c->device)
         return xr_fail(XRHIP_EINVAL, "xrhip_klt_join_group: the context and the group live on different devices");
+    if (g && lk_general(c))
+        return xr_fail(XRHIP_ESTATE, "xrhip_klt_join_group: a context with non-default LK parameters (xrhip_klt_set_lk_params) cannot join a group");
     // whatever the context has queued so far completes where it was queued
     {
         const int rc = flush_upload(c);
@@ -574,9 +603,10 @@ int xrhip_image_create(xrhip_klt *c, xrhip_image **out) {
     if (!c || !out) return xr_fail(XRHIP_EINVAL, "xrhip_image_create: null argument");
     xrhip_image *im = new xrhip_image();
     im->ctx = c;
+    im->levels = c->lk.max_level + 1;
     XR_HIP(hipMalloc(&im->raw, (size_t)c->w * c->h));
     int w = c->w, h = c->h;
-    for (int l = 0; l < KLT_LEVELS; ++l) {
+    for (int l = 0; l < im->levels; ++l) {
         LevelBuf &L = im->lv[l];
         L.w = w;
         L.h = h;
@@ -593,6 +623,7 @@ int xrhip_image_create(xrhip_klt *c, xrhip_image **out) {
         h = (h + 1) / 2;
     }
     XR_HIP(hipStreamSynchronize(c->stream));   // (the planes are cleared before any queue -- the context's or a group's -- can reach them)
+    c->n_images++;
     *out = im;
     return XRHIP_OK;
 }
@@ -605,10 +636,11 @@ void xrhip_image_destroy(xrhip_image *im) {
     if (im->ctx->group) group_drain(im->ctx->group, GQ_KLT, im->ctx);
     hipStreamSynchronize(im->ctx->stream);
     hipFree(im->raw);
-    for (int l = 0; l < KLT_LEVELS; ++l) {
+    for (int l = 0; l < im->levels; ++l) {
         hipFree(im->lv[l].img_base);
         hipFree(im->lv[l].der_base);
     }
+    im->ctx->n_images--;
     delete im;
 }
 
@@ -942,7 +974,7 @@ int xrhip_debug_set_fused_pyramid(xrhip_klt *c, int on) {
     return XRHIP_OK;
 }
 int xrhip_debug_get_level_padded(const xrhip_image *im, int level, uint8_t *out, int *rows, int *cols) {
-    if (!im || level < 0 || level >= KLT_LEVELS || !rows || !cols) return xr_fail(XRHIP_EINVAL, "xrhip_debug_get_level_padded: bad arguments");
+    if (!im || level < 0 || level >= im->levels || !rows || !cols) return xr_fail(XRHIP_EINVAL, "xrhip_debug_get_level_padded: bad arguments");
     if (!im->have_pyramid) return xr_fail(XRHIP_ESTATE, "xrhip_debug_get_level_padded: preprocess() has not run");
     const LevelBuf &L = im->lv[level];
     *rows = L.h + 2 * KLT_PAD;
@@ -1017,8 +1049,9 @@ int xrhip_image_preprocess(xrhip_image *im, double clip_limit, int tiles_x, int 
     ProfScope prof(c, CAT_PRE);
     // the pyramid and its derivatives: two launches (k_pyr_a, k_pyr_b) behind the LUT kernel when every level is large enough for its
     // border to be one reflection away, else (or with the development switch) the five launches they replace
-    bool fused = c->fused_pyramid;
-    for (int l = 0; l < KLT_LEVELS; ++l) fused = fused && im->lv[l].w >= 2 * KLT_PAD + 2 && im->lv[l].h >= 2 * KLT_PAD + 2;
+    const bool general = lk_general(c);   // any level count: the CLAHE plane, then a pyrDown and a Scharr launch per level
+    bool fused = c->fused_pyramid && !general;
+    for (int l = 0; l < KLT_LEVELS && fused; ++l) fused = fused && im->lv[l].w >= 2 * KLT_PAD + 2 && im->lv[l].h >= 2 * KLT_PAD + 2;
     ClaheLutArgs la{im->raw, w, w, h, tw, th, tiles_x, clip, lut_scale, c->lut, tiles};
     if (fused) {
         if (c->group) {
@@ -1076,6 +1109,18 @@ int xrhip_image_preprocess(xrhip_image *im, double clip_limit, int tiles_x, int 
             dim3 blk(64, 4);
             dim3 grd((w + 2 * KLT_PAD + 63) / 64, (h + 2 * KLT_PAD + 3) / 4);
             hipLaunchKernelGGL(k_clahe_apply, grd, blk, 0, st, im->raw, w, w, h, tw, th, tiles_x, tiles_y, c->lut, L.img, L.istride);
+        }
+        if (general) {
+            const PyrViewG pg = make_view_g(im);
+            for (int l = 1; l < im->levels; ++l) {
+                const LevelBuf &D = im->lv[l];
+                hipLaunchKernelGGL(k_pyrdown, dim3((D.w + 2 * KLT_PAD + 63) / 64, (D.h + 2 * KLT_PAD + 3) / 4), dim3(64, 4), 0, st, pg.lv[l - 1], D.img,
+                                   D.w, D.h, D.istride);
+            }
+            for (int l = 0; l < im->levels; ++l)
+                hipLaunchKernelGGL(k_scharr_level, dim3((im->lv[l].w + 63) / 64, (im->lv[l].h + 3) / 4), dim3(256), 0, st, pg.lv[l], im->lv[l].der);
+            XR_HIP(hipGetLastError());
+            return XRHIP_OK;
         }
         PyrView pv = make_view(im);
         for (int l = 1; l < KLT_LEVELS; ++l) {
@@ -1321,7 +1366,14 @@ int xrhip_image_track(const xrhip_image *cur, const xrhip_image *next, const dou
     } else {   // launched here: the two halves keep their own event pairs (bench.py's roofline_lk is the LK kernel alone)
         const bool with_detect = tp.detect;
         tp.detect = false;
-        rc = klt_issue(c, c->rq_track, GK_TRACK, &tp, launch_track_batch);
+        if (lk_general(c)) {   // (never a member of a group) the kernel with runtime parameters; what follows the launch is unchanged
+            const LkTrackGArgs ga{make_view_g(cur), make_view_g(next), lk_device_params(c), dv_curr, dv_next, has_guess ? 1 : 0, dv_status, n,
+                                  tp.lk.counters, c->d_done, c->done_base, d_seq, seq};
+            hipLaunchKernelGGL(k_lk_track_g, dim3(n), dim3(LK_THREADS), 0, c->stream, ga);
+            XR_HIP(hipGetLastError());
+        } else {
+            rc = klt_issue(c, c->rq_track, GK_TRACK, &tp, launch_track_batch);
+        }
         if (rc) return rc;
         prof.finish();
         if (with_detect) {
@@ -1361,8 +1413,14 @@ int xrhip_image_lk(const xrhip_image *prev, const xrhip_image *next, const float
     return klt_run_sync(c, [&](hipStream_t st) {
         XR_HIP(hipMemcpyAsync(c->d_fprev, prev_xy, sizeof(float2) * n, hipMemcpyHostToDevice, st));
         XR_HIP(hipMemcpyAsync(c->d_fnext, next_xy_inout, sizeof(float2) * n, hipMemcpyHostToDevice, st));
-        PyrView A = make_view(prev), B = make_view(next);
-        hipLaunchKernelGGL(k_lk_plain, dim3(n), dim3(LK_THREADS), 0, st, A, B, c->d_fprev, c->d_fnext, c->d_status, n);
+        if (lk_general(c)) {
+            const LkPlainGArgs ga{make_view_g(prev), make_view_g(next), lk_device_params(c), c->d_fprev, c->d_fnext, c->d_status, n,
+                                  c->profiling ? c->d_counters : (LkCounters *)nullptr};
+            hipLaunchKernelGGL(k_lk_plain_g, dim3(n), dim3(LK_THREADS), 0, st, ga);
+        } else {
+            PyrView A = make_view(prev), B = make_view(next);
+            hipLaunchKernelGGL(k_lk_plain, dim3(n), dim3(LK_THREADS), 0, st, A, B, c->d_fprev, c->d_fnext, c->d_status, n);
+        }
         XR_HIP(hipGetLastError());
         XR_HIP(hipMemcpyAsync(status, c->d_status, n, hipMemcpyDeviceToHost, st));
         XR_HIP(hipMemcpyAsync(next_xy_inout, c->d_fnext, sizeof(float2) * n, hipMemcpyDeviceToHost, st));
@@ -1371,14 +1429,14 @@ int xrhip_image_lk(const xrhip_image *prev, const xrhip_image *next, const float
 }
 
 int xrhip_image_level_dims(const xrhip_image *im, int level, int *w, int *h) {
-    if (!im || level < 0 || level >= KLT_LEVELS || !w || !h) return xr_fail(XRHIP_EINVAL, "xrhip_image_level_dims: bad arguments");
+    if (!im || level < 0 || level >= im->levels || !w || !h) return xr_fail(XRHIP_EINVAL, "xrhip_image_level_dims: bad arguments");
     *w = im->lv[level].w;
     *h = im->lv[level].h;
     return XRHIP_OK;
 }
 
 int xrhip_image_download_level(const xrhip_image *im, int level, uint8_t *img_out, int16_t *deriv_out) {
-    if (!im || level < 0 || level >= KLT_LEVELS) return xr_fail(XRHIP_EINVAL, "xrhip_image_download_level: bad arguments");
+    if (!im || level < 0 || level >= im->levels) return xr_fail(XRHIP_EINVAL, "xrhip_image_download_level: bad arguments");
     if (!im->have_pyramid) return xr_fail(XRHIP_ESTATE, "xrhip_image_download_level: preprocess() has not run");
     const LevelBuf &L = im->lv[level];
     xrhip_klt *c = im->ctx;
@@ -1408,6 +1466,60 @@ int xrhip_image_download_harris(xrhip_image *im, float *resp_out) {
         XR_HIP(hipMemcpyAsync(c->max_key, init, sizeof(init), hipMemcpyHostToDevice, st));
         return XRHIP_OK;
     });
+}
+
+int xrhip_klt_set_lk_params(xrhip_klt *c, const xrhip_lk_params *p) {
+    if (!c) return xr_fail(XRHIP_EINVAL, "xrhip_klt_set_lk_params: null context");
+    const xrhip_lk_params def{XRHIP_KLT_WIN, XRHIP_KLT_LEVELS - 1, 30, 0.01};
+    const xrhip_lk_params q = p ? *p : def;
+    char msg[256];
+    if (q.win < 5 || q.win > 21 || q.win % 2 == 0) {
+        std::snprintf(msg, sizeof(msg), "xrhip_klt_set_lk_params: win = %d: the window is odd, 5..21", q.win);
+        return xr_fail(XRHIP_EINVAL, msg);
+    }
+    if (q.max_level < 0 || q.max_level > KLT_MAX_LEVELS - 1) {
+        std::snprintf(msg, sizeof(msg), "xrhip_klt_set_lk_params: max_level = %d: 0..%d", q.max_level, KLT_MAX_LEVELS - 1);
+        return xr_fail(XRHIP_EINVAL, msg);
+    }
+    if (q.max_count < 1 || q.max_count > 100) {
+        std::snprintf(msg, sizeof(msg), "xrhip_klt_set_lk_params: max_count = %d: 1..100", q.max_count);
+        return xr_fail(XRHIP_EINVAL, msg);
+    }
+    if (!(q.epsilon >= 0.0 && q.epsilon <= 10.0)) {
+        std::snprintf(msg, sizeof(msg), "xrhip_klt_set_lk_params: epsilon = %g: 0..10", q.epsilon);
+        return xr_fail(XRHIP_EINVAL, msg);
+    }
+    // cv::buildOpticalFlowPyramid stops before a level that is not larger than the window; here that is an argument check.  (The
+    // reference's own pair, 21 / 3, is what every context has always run, at any frame size: it stays accepted.)
+    if (!(q.win == def.win && q.max_level == def.max_level)) {
+        int tw = c->w, th = c->h;
+        for (int l = 0; l < q.max_level; ++l) {
+            tw = (tw + 1) / 2;
+            th = (th + 1) / 2;
+        }
+        if (tw <= q.win || th <= q.win) {
+            std::snprintf(msg, sizeof(msg), "xrhip_klt_set_lk_params: max_level = %d: level %d of a %d x %d frame is %d x %d, not larger than win = %d",
+                          q.max_level, q.max_level, c->w, c->h, tw, th, q.win);
+            return xr_fail(XRHIP_EINVAL, msg);
+        }
+    }
+    if (c->group)
+        return xr_fail(XRHIP_ESTATE, "xrhip_klt_set_lk_params: the context is a member of a group (its shared launches are the specialised kernels)");
+    if (c->n_images > 0)
+        return xr_fail(XRHIP_ESTATE, "xrhip_klt_set_lk_params: the context has images (their pyramid storage is sized by max_level): set the parameters first");
+    c->lk = q;
+    return XRHIP_OK;
+}
+int xrhip_klt_get_lk_params(const xrhip_klt *c, xrhip_lk_params *out) {
+    if (!c || !out) return xr_fail(XRHIP_EINVAL, "xrhip_klt_get_lk_params: null argument");
+    *out = c->lk;
+    return XRHIP_OK;
+}
+int xrhip_debug_force_general_lk(xrhip_klt *c, int on) {
+    if (!c) return xr_fail(XRHIP_EINVAL, "xrhip_debug_force_general_lk: null context");
+    if (on && c->group) return xr_fail(XRHIP_ESTATE, "xrhip_debug_force_general_lk: the context is a member of a group");
+    c->force_general = on != 0;
+    return XRHIP_OK;
 }
 
 int xrhip_klt_set_profiling(xrhip_klt *c, int enable) {

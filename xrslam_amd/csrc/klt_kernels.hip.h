@@ -1807,4 +1807,408 @@ __global__ __launch_bounds__(LK_THREADS) void k_lk_plain(PyrView A, PyrView B, c
     }
 }
 
+// ------------------------------------------------------------------------------------- LK with runtime parameters (xrhip_klt_set_lk_params)
+// The kernels above are unrolled on the reference's constants: a 21-pixel window, four levels, 30 iterations, epsilon 0.01.  A context
+// whose parameters differ (or whose development switch is on) runs the kernels below instead: the same arithmetic -- exact integer window
+// sums converted to float once, scalar IEEE float per point, the oracle's order of decisions per level -- with the window (odd, 5..21),
+// the number of levels (1..KLT_MAX_LEVELS), the iteration cap and the squared epsilon read from the argument block.
+//   * One workgroup per point, LK_WAVES wavefronts, pixel p = tid + LK_THREADS * slot as above: win * win <= 441 fills at most the
+//     two slots of a lane, the lanes beyond win * win carry zeros.
+//   * The level loop is a RUNTIME loop and nothing is kept per level: a level's template is gathered, its search tile fetched (around
+//     the position the coarser level ended at) and its A sums exchanged when the level is reached, as k_lk_track did before its requests
+//     were hoisted in front of the first level.  What lives across the loop is the running position and the status: no array indexed by
+//     the level, hence nothing for the compiler to put into scratch.  A level's view is read from the kernel-argument segment
+//     (lkg_level) for the same reason.
+//   * The search tile is sized from the window: (win + 1 + 2 * LK_TILE_R) rows of whole dwords; an iterate whose footprint leaves it
+//     reads global memory, as above.  win <= 21 = KLT_PAD keeps every footprint of a valid iterate inside the padded plane.
+constexpr int KLT_MAX_LEVELS = 6;
+struct PyrViewG {
+    LevelView lv[KLT_MAX_LEVELS];
+};
+struct LkParams {
+    int win;         // odd, 5..21
+    int levels;      // max_level + 1
+    int max_count;   // 1..100
+    double eps2;     // epsilon squared, compared in double
+};
+// A pyramid's level views where the dispatch put them: the kernel-argument segment, read through the constant address space.  The
+// level index is a runtime value; indexing the by-value argument struct with it makes the compiler keep a copy of the struct in
+// scratch (392 bytes per lane in the first build, also with a chain of selects, which it folds back into one indexed load), whereas
+// an indexed read of the segment itself is one scalar load.  `offset`: of the PyrViewG inside the kernel's only argument.
+typedef const __attribute__((address_space(4))) LevelView *lkg_levels;
+__device__ __forceinline__ lkg_levels lkg_kernarg_levels(size_t offset) {
+    return (lkg_levels)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + offset);
+}
+__device__ __forceinline__ LevelView lkg_level(lkg_levels P, int level) {
+    LevelView L;
+    L.img = P[level].img;
+    L.der = P[level].der;
+    L.w = P[level].w;
+    L.h = P[level].h;
+    L.istride = P[level].istride;
+    L.pstride = P[level].pstride;
+    return L;
+}
+
+// cv::detail::calcSharrDeriv of ONE level (k_scharr's arithmetic; its argument block is four levels wide): 64x4 pixels per workgroup
+__global__ __launch_bounds__(256) void k_scharr_level(LevelView L, short2 *__restrict__ out) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= L.w || y >= L.h) return;
+    const uint8_t *r0 = L.img + (ptrdiff_t)(y - 1) * L.istride + x;
+    const uint8_t *r1 = r0 + L.istride;
+    const uint8_t *r2 = r1 + L.istride;
+    const int t0m = (r0[-1] + r2[-1]) * 3 + r1[-1] * 10;
+    const int t0p = (r0[1] + r2[1]) * 3 + r1[1] * 10;
+    const int t1m = r2[-1] - r0[-1];
+    const int t1c = r2[0] - r0[0];
+    const int t1p = r2[1] - r0[1];
+    short2 d;
+    d.x = (short)(t0p - t0m);
+    d.y = (short)((t1p + t1m) * 3 + t1c * 10);
+    out[(ptrdiff_t)y * L.pstride + x] = d;
+}
+
+__device__ __forceinline__ void lkg_lane_layout(int lane, int win, int (&wx)[LK_SLOTS], int (&wy)[LK_SLOTS], bool (&wvalid)[LK_SLOTS]) {
+#pragma unroll
+    for (int s = 0; s < LK_SLOTS; ++s) {
+        int p = lane + LK_THREADS * s;
+        wvalid[s] = p < win * win;
+        if (!wvalid[s]) p = 0;
+        wy[s] = p / win;
+        wx[s] = p - wy[s] * win;
+    }
+}
+
+// One direction for one point, as lk_one_way.  tile: LK_TILE_DWORDS of LDS; xch: [2][LK_WAVES][4] doubles (the A sums of a level, or the
+// four half sums of an iteration in the first 16 bytes of a wavefront's slot), alternating halves so that one barrier per exchange suffices.
+// Every branch that contains a barrier is taken by all lanes of the workgroup alike: they carry the same scalar state.
+__device__ __forceinline__ int lkg_one_way(lkg_levels A, lkg_levels B, const LkParams &P, float px0, float py0, float &nx_io,
+                                           float &ny_io, const int (&wx)[LK_SLOTS], const int (&wy)[LK_SLOTS], const bool (&wvalid)[LK_SLOTS],
+                                           unsigned &n_templates, unsigned &n_iters, uint32_t *tile, double (*xch)[LK_WAVES][4], int &xpar) {
+    static_assert(LK_SLOTS <= 2, "the 32-bit wavefront sums below hold two slots per lane");
+    const int wave_id = (int)threadIdx.x >> 6;
+    const int win = P.win;
+    const float FLT_SCALE = 1.f / (1 << 20);
+    const float half = (win - 1) * 0.5f;
+    const int foot = win + 1;                                    // the window and its bilinear neighbours
+    const int tile_w4 = (foot + 2 * LK_TILE_R + 3 + 3) >> 2;     // + up to 3 pixels of alignment slack, whole dwords
+    const int tile_w = 4 * tile_w4, tile_h = foot + 2 * LK_TILE_R;
+    const int tile_dwords = tile_h * tile_w4;                    // <= LK_TILE_DWORDS (win <= 21)
+    const float min_eig_div = (float)(2 * win * win);
+    typedef uint16_t __attribute__((aligned(1))) lk_u16u;
+    typedef uint2 __attribute__((aligned(4))) lk_u2u;
+    int status = 1;
+    float outx = nx_io, outy = ny_io;
+    for (int level = P.levels - 1; level >= 0; --level) {
+        const LevelView I = lkg_level(A, level), J = lkg_level(B, level);
+        const float lscale = __int_as_float((127 - level) << 23);   // 2^-level
+        float nx, ny;
+        if (level == P.levels - 1) {
+            nx = outx * lscale;
+            ny = outy * lscale;
+        } else {
+            nx = outx * 2.f;
+            ny = outy * 2.f;
+        }
+        outx = nx;
+        outy = ny;
+        const float px = px0 * lscale - half, py = py0 * lscale - half;
+        const int ipx = (int)floorf(px), ipy = (int)floorf(py);
+        if (ipx < -win || ipx >= I.w || ipy < -win || ipy >= I.h) {
+            if (level == 0) status = 0;
+            continue;
+        }
+        // ---- requests: the search tile around this level's starting position, then the template samples
+        bool staged = false;
+        int tx0 = 0, ty0 = 0;
+        uint32_t tile_regs[LK_TILE_LOADS];
+        if (LK_STAGE_J) {
+            const int inx0 = (int)floorf(nx - half), iny0 = (int)floorf(ny - half);
+            if (inx0 >= -win && inx0 < J.w && iny0 >= -win && iny0 < J.h) {
+                int x0 = inx0 - LK_TILE_R;
+                const int y0 = iny0 - LK_TILE_R;
+                x0 -= (int)(reinterpret_cast<uintptr_t>(J.img + x0) & 3);   // row strides are multiples of 64 bytes
+#pragma unroll
+                for (int k = 0; k < LK_TILE_LOADS; ++k) {
+                    const int idx = min((int)threadIdx.x + LK_THREADS * k, tile_dwords - 1);
+                    const int r = idx / tile_w4, c4 = idx - r * tile_w4;
+                    // rows / dwords outside the padded plane are never part of a valid footprint: clamp the address
+                    const int y = min(max(y0 + r, -KLT_PAD), J.h + KLT_PAD - 1);
+                    const int x = min(max(x0 + 4 * c4, -KLT_PADX), J.istride - KLT_PADX - 4);
+                    tile_regs[k] = *reinterpret_cast<const uint32_t *>(J.img + (ptrdiff_t)y * J.istride + x);
+                }
+                tx0 = x0;
+                ty0 = y0;
+                staged = true;
+            }
+        }
+        const float ta = px - ipx, tb = py - ipy;
+        const int tw00 = __float2int_rn((1.f - ta) * (1.f - tb) * (1 << LK_W_BITS));
+        const int tw01 = __float2int_rn(ta * (1.f - tb) * (1 << LK_W_BITS));
+        const int tw10 = __float2int_rn((1.f - ta) * tb * (1 << LK_W_BITS));
+        const int tw11 = (1 << LK_W_BITS) - tw00 - tw01 - tw10;
+        uint32_t raw_i[LK_SLOTS][2];
+        uint2 raw_d[LK_SLOTS][2];
+#pragma unroll
+        for (int sl = 0; sl < LK_SLOTS; ++sl) {
+            const uint8_t *s0 = I.img + (ptrdiff_t)(ipy + wy[sl]) * I.istride + (ipx + wx[sl]);
+            const uint8_t *s1 = s0 + I.istride;
+            const short2 *d0 = I.der + (ptrdiff_t)(ipy + wy[sl]) * I.pstride + (ipx + wx[sl]);
+            const short2 *d1 = d0 + I.pstride;
+            raw_i[sl][0] = *reinterpret_cast<const lk_u16u *>(s0);
+            raw_i[sl][1] = *reinterpret_cast<const lk_u16u *>(s1);
+            raw_d[sl][0] = *reinterpret_cast<const lk_u2u *>(d0);
+            raw_d[sl][1] = *reinterpret_cast<const lk_u2u *>(d1);
+        }
+        // ---- the tile goes to LDS (every wavefront is past its last read of the previous tile: the exchange barrier of an iteration
+        // comes after its taps), the template is formed, its A sums reduced inside the wavefront
+        if (staged) {
+#pragma unroll
+            for (int k = 0; k < LK_TILE_LOADS; ++k) {
+                const int idx = (int)threadIdx.x + LK_THREADS * k;
+                if (idx < tile_dwords) tile[idx] = tile_regs[k];
+            }
+        }
+        int Iv[LK_SLOTS], Ix[LK_SLOTS], Iy[LK_SLOTS];
+        int sA11 = 0, sA12 = 0, sA22 = 0;   // |Ix|, |Iy| <= 4080: two slots stay below 2^25 per lane, 64 lanes below 2^31
+#pragma unroll
+        for (int sl = 0; sl < LK_SLOTS; ++sl) {
+            const uint32_t r0 = raw_i[sl][0], r1 = raw_i[sl][1];
+            const uint2 e0 = raw_d[sl][0], e1 = raw_d[sl][1];   // .x: (Ix, Iy) of the left pixel, .y: of the right one
+            int ival = lk_descale(lk_tap((int)(r0 & 255u), tw00) + lk_tap((int)(r0 >> 8), tw01) + lk_tap((int)(r1 & 255u), tw10) + lk_tap((int)(r1 >> 8), tw11),
+                                  LK_W_BITS - 5);
+            int ixval = lk_descale(lk_tap((int)(short)(e0.x & 0xffffu), tw00) + lk_tap((int)(short)(e0.y & 0xffffu), tw01) +
+                                       lk_tap((int)(short)(e1.x & 0xffffu), tw10) + lk_tap((int)(short)(e1.y & 0xffffu), tw11),
+                                   LK_W_BITS);
+            int iyval = lk_descale(lk_tap((int)e0.x >> 16, tw00) + lk_tap((int)e0.y >> 16, tw01) + lk_tap((int)e1.x >> 16, tw10) + lk_tap((int)e1.y >> 16, tw11),
+                                   LK_W_BITS);
+            // OpenCV stores these as int16; a lane without a pixel in this slot carries zeros
+            ival = wvalid[sl] ? (int)(short)ival : 0;
+            ixval = wvalid[sl] ? (int)(short)ixval : 0;
+            iyval = wvalid[sl] ? (int)(short)iyval : 0;
+            Iv[sl] = ival;
+            Ix[sl] = ixval;
+            Iy[sl] = iyval;
+            sA11 += ixval * ixval;
+            sA12 += ixval * iyval;
+            sA22 += iyval * iyval;
+        }
+        const double pA11 = (double)dpp_scan_add_i32(sA11), pA12 = (double)dpp_scan_add_i32(sA12), pA22 = (double)dpp_scan_add_i32(sA22);
+        if ((threadIdx.x & 63) == 0) {
+            xch[xpar][wave_id][0] = pA11;
+            xch[xpar][wave_id][1] = pA12;
+            xch[xpar][wave_id][2] = pA22;
+        }
+        __syncthreads();   // (publishes the tile as well)
+        double dA11 = 0.0, dA12 = 0.0, dA22 = 0.0;   // exact integers below 2^53: the same sum in any order
+#pragma unroll
+        for (int w = 0; w < LK_WAVES; ++w) {
+            dA11 += xch[xpar][w][0];
+            dA12 += xch[xpar][w][1];
+            dA22 += xch[xpar][w][2];
+        }
+        xpar ^= 1;
+        n_templates++;
+        const float A11 = (float)dA11 * FLT_SCALE, A12 = (float)dA12 * FLT_SCALE, A22 = (float)dA22 * FLT_SCALE;
+        float D = A11 * A22 - A12 * A12;
+        const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / min_eig_div;
+        if (minEig < 1e-4f || D < 1.1920929e-07f) {
+            if (level == 0) status = 0;
+            continue;
+        }
+        D = 1.f / D;
+        nx -= half;
+        ny -= half;
+        float pdx = 0.f, pdy = 0.f;
+        for (int j = 0; j < P.max_count; ++j) {
+            const int inx = (int)floorf(nx), iny = (int)floorf(ny);
+            if (inx < -win || inx >= J.w || iny < -win || iny >= J.h) {
+                if (level == 0) status = 0;
+                break;
+            }
+            const float a = nx - inx, b = ny - iny;
+            const int iw00 = __float2int_rn((1.f - a) * (1.f - b) * (1 << LK_W_BITS));
+            const int iw01 = __float2int_rn(a * (1.f - b) * (1 << LK_W_BITS));
+            const int iw10 = __float2int_rn((1.f - a) * b * (1 << LK_W_BITS));
+            const int iw11 = (1 << LK_W_BITS) - iw00 - iw01 - iw10;
+            // per-lane partial sums stay in 32 bits: |diff| <= 8160, |Ix|, |Iy| <= 4080, two slots: < 6.7e7
+            int sb1 = 0, sb2 = 0;
+            const int rx = inx - tx0, ry = iny - ty0;
+            if (staged && rx >= 0 && rx <= tile_w - foot && ry >= 0 && ry <= tile_h - foot) {
+                typedef const __attribute__((address_space(3))) uint8_t *lds_bytes;
+                const lds_bytes t = (lds_bytes)tile + ry * tile_w + rx;
+#pragma unroll
+                for (int sl = 0; sl < LK_SLOTS; ++sl) {
+                    const lds_bytes j0 = t + wy[sl] * tile_w + wx[sl];
+                    const lds_bytes j1 = j0 + tile_w;
+                    int acc = lk_tap_acc(j0[0], iw00, 1 << (LK_W_BITS - 5 - 1));   // the rounding term of lk_descale rides along
+                    acc = lk_tap_acc(j0[1], iw01, acc);
+                    acc = lk_tap_acc(j1[0], iw10, acc);
+                    acc = lk_tap_acc(j1[1], iw11, acc);
+                    const int diff = (acc >> (LK_W_BITS - 5)) - Iv[sl];
+                    sb1 = lk_tap_acc(diff, Ix[sl], sb1);
+                    sb2 = lk_tap_acc(diff, Iy[sl], sb2);
+                }
+            } else {
+#pragma unroll
+                for (int sl = 0; sl < LK_SLOTS; ++sl) {
+                    const uint8_t *j0 = J.img + (ptrdiff_t)(iny + wy[sl]) * J.istride + (inx + wx[sl]);
+                    const uint8_t *j1 = j0 + J.istride;
+                    int acc = lk_tap_acc(j0[0], iw00, 1 << (LK_W_BITS - 5 - 1));
+                    acc = lk_tap_acc(j0[1], iw01, acc);
+                    acc = lk_tap_acc(j1[0], iw10, acc);
+                    acc = lk_tap_acc(j1[1], iw11, acc);
+                    const int diff = (acc >> (LK_W_BITS - 5)) - Iv[sl];
+                    sb1 = lk_tap_acc(diff, Ix[sl], sb1);
+                    sb2 = lk_tap_acc(diff, Iy[sl], sb2);
+                }
+            }
+            n_iters++;
+            // low (unsigned) and high (signed) 16-bit halves summed separately, each below 2^22 per wavefront; recombined in double
+            int h4[4] = {dpp_scan_add_i32(sb1 & 0xffff), dpp_scan_add_i32(sb1 >> 16), dpp_scan_add_i32(sb2 & 0xffff), dpp_scan_add_i32(sb2 >> 16)};
+            if (LK_WAVES > 1) {
+                int4 *slots = reinterpret_cast<int4 *>(&xch[xpar][0][0]);   // one 32-byte slot per wavefront: its first 16 bytes
+                if ((threadIdx.x & 63) == 0) slots[2 * wave_id] = make_int4(h4[0], h4[1], h4[2], h4[3]);
+                __syncthreads();
+                h4[0] = h4[1] = h4[2] = h4[3] = 0;
+#pragma unroll
+                for (int w = 0; w < LK_WAVES; ++w) {
+                    const int4 v = slots[2 * w];
+                    h4[0] += v.x;
+                    h4[1] += v.y;
+                    h4[2] += v.z;
+                    h4[3] += v.w;
+                }
+                xpar ^= 1;
+            }
+            const double db1 = (double)h4[1] * 65536.0 + (double)h4[0], db2 = (double)h4[3] * 65536.0 + (double)h4[2];
+            const float b1 = (float)db1 * FLT_SCALE;
+            const float b2 = (float)db2 * FLT_SCALE;
+            const float dx = (A12 * b2 - A22 * b1) * D;
+            const float dy = (A12 * b1 - A11 * b2) * D;
+            nx += dx;
+            ny += dy;
+            outx = nx + half;
+            outy = ny + half;
+            if ((double)dx * (double)dx + (double)dy * (double)dy <= P.eps2) break;
+            if (j > 0 && fabs((double)(dx + pdx)) < 0.01 && fabs((double)(dy + pdy)) < 0.01) {
+                outx -= dx * 0.5f;
+                outy -= dy * 0.5f;
+                break;
+            }
+            pdx = dx;
+            pdy = dy;
+        }
+    }
+    nx_io = outx;
+    ny_io = outy;
+    return status;
+}
+
+// OpenCvImage::track_keypoints with runtime LK parameters: forward LK, the 20-pixel border and rows / 4 displacement gates, backward LK,
+// the 0.5-pixel round trip -- d_lk_track's gates, result stores, counters and completion mailbox.
+struct LkTrackGArgs {
+    PyrViewG A, B;
+    LkParams P;
+    const double2 *curr;
+    double2 *next_io;
+    int has_guess;
+    uint8_t *status_out;
+    int n;
+    LkCounters *counters;
+    unsigned *done;
+    unsigned done_target;
+    int *host_seq;
+    int seq;
+};
+__global__ __launch_bounds__(LK_THREADS) void k_lk_track_g(LkTrackGArgs a) {
+    const int pt = blockIdx.x;
+    if (pt >= a.n) return;
+    const int lane = threadIdx.x;
+    int wx[LK_SLOTS], wy[LK_SLOTS];
+    bool wvalid[LK_SLOTS];
+    lkg_lane_layout(lane, a.P.win, wx, wy, wvalid);
+    const double2 c = a.curr[pt];
+    const float cx = (float)c.x, cy = (float)c.y;   // to_opencv(): double -> float
+    float nx = cx, ny = cy;
+    if (a.has_guess) {
+        const double2 g = a.next_io[pt];
+        nx = (float)g.x;
+        ny = (float)g.y;
+    }
+    unsigned n_templates = 0, n_iters = 0;
+    __shared__ uint32_t tile[LK_TILE_DWORDS];
+    __shared__ __attribute__((aligned(16))) double xch[2][LK_WAVES][4];
+    int xpar = 0;
+    const lkg_levels lvA = lkg_kernarg_levels(offsetof(LkTrackGArgs, A)), lvB = lkg_kernarg_levels(offsetof(LkTrackGArgs, B));
+    int status = lkg_one_way(lvA, lvB, a.P, cx, cy, nx, ny, wx, wy, wvalid, n_templates, n_iters, tile, xch, xpar);
+    const int cols = a.A.lv[0].w, rows = a.A.lv[0].h;
+    if (nx < 20 || nx >= cols - 20 || ny < 20 || ny >= rows - 20) status = 0;
+    if (status) {
+        const float dx = nx - cx, dy = ny - cy;
+        const double nrm = sqrt((double)dx * (double)dx + (double)dy * (double)dy);
+        if (nrm > rows / 4) status = 0;
+    }
+    if (status) {
+        float rx = cx, ry = cy;
+        const int st2 = lkg_one_way(lvB, lvA, a.P, nx, ny, rx, ry, wx, wy, wvalid, n_templates, n_iters, tile, xch, xpar);
+        const float dx = cx - rx, dy = cy - ry;
+        const double nrm = sqrt((double)dx * (double)dx + (double)dy * (double)dy);
+        if (!st2 || nrm > 0.5) status = 0;
+    }
+    if (lane == 0) {
+        host_store(&a.status_out[pt], (uint8_t)status);
+        if (status) {
+            host_store(&a.next_io[pt].x, (double)nx);
+            host_store(&a.next_io[pt].y, (double)ny);
+        }
+        if (a.counters) {
+            atomicAdd(&a.counters->templates, (unsigned long long)n_templates);
+            atomicAdd(&a.counters->iterations, (unsigned long long)n_iters);
+        }
+        if (a.done) {
+            __threadfence_system();
+            if (atomicAdd(a.done, 1u) + 1u == a.done_target) {
+                __threadfence_system();
+                host_store(a.host_seq, a.seq);
+            }
+        }
+    }
+}
+
+// plain calcOpticalFlowPyrLK with runtime parameters (float in/out, every point) -- parity aid, k_lk_plain's general form
+struct LkPlainGArgs {
+    PyrViewG A, B;
+    LkParams P;
+    const float2 *prev;
+    float2 *next_io;
+    uint8_t *status_out;
+    int n;
+    LkCounters *counters;
+};
+__global__ __launch_bounds__(LK_THREADS) void k_lk_plain_g(LkPlainGArgs a) {
+    const int pt = blockIdx.x;
+    if (pt >= a.n) return;
+    const int lane = threadIdx.x;
+    int wx[LK_SLOTS], wy[LK_SLOTS];
+    bool wvalid[LK_SLOTS];
+    lkg_lane_layout(lane, a.P.win, wx, wy, wvalid);
+    const float2 p = a.prev[pt];
+    float2 q = a.next_io[pt];
+    unsigned n_templates = 0, n_iters = 0;
+    __shared__ uint32_t tile[LK_TILE_DWORDS];
+    __shared__ __attribute__((aligned(16))) double xch[2][LK_WAVES][4];
+    int xpar = 0;
+    const int status = lkg_one_way(lkg_kernarg_levels(offsetof(LkPlainGArgs, A)), lkg_kernarg_levels(offsetof(LkPlainGArgs, B)), a.P, p.x, p.y, q.x, q.y, wx, wy, wvalid, n_templates, n_iters, tile, xch, xpar);
+    if (lane == 0) {
+        a.status_out[pt] = (uint8_t)status;
+        a.next_io[pt] = q;
+        if (a.counters) {
+            atomicAdd(&a.counters->templates, (unsigned long long)n_templates);
+            atomicAdd(&a.counters->iterations, (unsigned long long)n_iters);
+        }
+    }
+}
+
 }   // namespace xrhip

@@ -17,6 +17,14 @@ class KltStats(C.Structure):
                 ("detect_full_list", C.c_longlong)]
 
 
+class LkParams(C.Structure):
+    """xrhip_lk_params: cv::calcOpticalFlowPyrLK's winSize (square), maxLevel and criteria."""
+    _fields_ = [("win", C.c_int), ("max_level", C.c_int), ("max_count", C.c_int), ("epsilon", C.c_double)]
+
+
+LK_DEFAULTS = (21, 3, 30, 0.01)   # the reference's (opencv_image.cpp:96-99)
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -57,6 +65,9 @@ def _bind():
     L.xrhip_debug_get_level_padded.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.xrhip_image_render_view.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]
     L.xrhip_debug_view_timing.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_int]
+    L.xrhip_klt_set_lk_params.argtypes = [vp, C.POINTER(LkParams)]
+    L.xrhip_klt_get_lk_params.argtypes = [vp, C.POINTER(LkParams)]
+    L.xrhip_debug_force_general_lk.argtypes = [vp, C.c_int]
     return L
 
 
@@ -119,6 +130,28 @@ class KltContext:
     def set_fused_pyramid(self, on):
         """Development / parity switch: preprocess() builds the pyramid in one launch (default) or in the five it replaces."""
         check(L().xrhip_debug_set_fused_pyramid(self._h, 1 if on else 0))
+
+    def set_lk_params(self, win=None, max_level=None, max_count=None, epsilon=None):
+        """Lucas-Kanade window (odd, 5..21), pyramid depth (0..5), iteration cap (1..100) and stop threshold (0..10) of this context;
+        an argument left None takes the reference's value, no arguments at all restore 21 / 3 / 30 / 0.01.  Before the first image:
+        the images' pyramid storage is sized by max_level.  HipImage.lk / track_keypoints need no new arguments."""
+        if win is None and max_level is None and max_count is None and epsilon is None:
+            check(L().xrhip_klt_set_lk_params(self._h, None))
+            return
+        d = LK_DEFAULTS
+        p = LkParams(int(d[0] if win is None else win), int(d[1] if max_level is None else max_level),
+                     int(d[2] if max_count is None else max_count), float(d[3] if epsilon is None else epsilon))
+        check(L().xrhip_klt_set_lk_params(self._h, C.byref(p)))
+
+    def get_lk_params(self):
+        """-> (win, max_level, max_count, epsilon)"""
+        p = LkParams()
+        check(L().xrhip_klt_get_lk_params(self._h, C.byref(p)))
+        return p.win, p.max_level, p.max_count, p.epsilon
+
+    def force_general_lk(self, on):
+        """Parity / measurement switch: the kernels with runtime parameters also at the reference's values."""
+        check(L().xrhip_debug_force_general_lk(self._h, 1 if on else 0))
 
     def set_undistort_map(self, map2):
         """Packed 1/32-pixel inverse map [h][w][2] uint32 (include/xrslam_hip.h), or None to switch the device
