@@ -269,6 +269,29 @@ void XRSLAMAmdSetProfiling(int enable);
 void XRSLAMAmdGetKltStats(void *xrhip_klt_stats_out, int reset);
 /* same for the BA context: xrhip_ba_stats from xrslam_hip.h (XRSLAMAmdSetProfiling switches both) */
 void XRSLAMAmdGetBaStats(void *xrhip_ba_stats_out, int reset);
+/* Covariance of the estimate (replaces: nothing the reference has; its users ask ceres::Covariance).  While enabled, every window
+ * solve (a keyframe's refine_window) is followed by xrhip_ba_covariance (xrslam_hip.h) on the solved problem, for the newest keyframe
+ * of the window; the answer stays, with its own timestamp, until the next window solve.  Off (the default) nothing is launched,
+ * allocated or written that was not before.  The poses, landmarks and every other output are the same either way.
+ *   state     15 x 15, error-state order dq dp dv dbg dba, in the body frame (the tangent space the solver works on)
+ *   pose_ros  the pose part permuted for nav_msgs/Odometry: x y z, rotation about x y z, i.e. pose_ros[i][j] = state[p(i)][p(j)] with
+ *             p = 3 4 5 0 1 2
+ *   status    as xrhip_cov_request.status (0 ok, 1 not positive definite / rank deficient, 2 nothing free); -1 before the first window
+ *             solve, and always with a library without xrhip_ba_covariance (XRSLAMAmdLastError says so)
+ * XRSLAMAmdGetCovariance returns 1 when a covariance is available (status 0), else 0; `out` is filled either way.
+ * XRSLAMAmdGetLandmarkVariances: the variance of the inverse depth of the landmarks that were free in that solve and are still valid
+ * (the set XRSLAM_RESULT_LANDMARKS draws from), with their track ids; returns the count available and writes min(count, cap) entries
+ * (either array may be NULL).  In pipelined mode both wait for the frame in flight, like XRSLAM_RESULT_LANDMARKS. */
+typedef struct XRSLAMAmdCovariance {
+    double timestamp;
+    double state[15][15];
+    double pose_ros[6][6];
+    int status;
+    double rcond_estimate;
+} XRSLAMAmdCovariance;
+void XRSLAMAmdSetCovariance(int enable);
+int XRSLAMAmdGetCovariance(XRSLAMAmdCovariance *out);
+int XRSLAMAmdGetLandmarkVariances(double *inv_depth_var, long long *track_ids, int cap);
 /* What the initialiser (core/initializer.cpp) did so far: attempts that reached SfM, whether the last one
  * succeeded, which of the eight (R, T) hypotheses won its triangulation vote, and the IMU alignment it produced
  * (metric scale of the unit-baseline SfM map, gravity in the SfM frame, gyroscope bias). */
@@ -362,6 +385,9 @@ void XRSLAMAmdInstanceSetDeviceUndistort(XRSLAMAmdInstance *inst, const char *mo
 void XRSLAMAmdInstanceGetTimes(XRSLAMAmdInstance *inst, XRSLAMAmdTimes *out);
 void XRSLAMAmdInstanceSetProfiling(XRSLAMAmdInstance *inst, int enable);
 void XRSLAMAmdInstanceGetBaStats(XRSLAMAmdInstance *inst, void *xrhip_ba_stats_out, int reset);
+void XRSLAMAmdInstanceSetCovariance(XRSLAMAmdInstance *inst, int enable);
+int XRSLAMAmdInstanceGetCovariance(XRSLAMAmdInstance *inst, XRSLAMAmdCovariance *out);
+int XRSLAMAmdInstanceGetLandmarkVariances(XRSLAMAmdInstance *inst, double *inv_depth_var, long long *track_ids, int cap);
 void XRSLAMAmdInstanceGetKltStats(XRSLAMAmdInstance *inst, void *xrhip_klt_stats_out, int reset);
 int XRSLAMAmdInstanceGetTrackerParams(XRSLAMAmdInstance *inst, XRSLAMAmdTrackerParams *out);
 void XRSLAMAmdInstanceGetInitReport(XRSLAMAmdInstance *inst, XRSLAMAmdInitReport *out);

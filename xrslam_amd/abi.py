@@ -38,6 +38,11 @@ class BaSummary(C.Structure):
                 ("ms_solve", C.c_double)]
 
 
+class CovRequest(C.Structure):   # xrhip_cov_request
+    _fields_ = [("n_sel", C.c_int), ("sel_frames", _ip), ("out_blocks", _dp), ("out_inv_depth_var", _dp), ("status", _ip),
+                ("rcond_estimate", _dp)]
+
+
 class MargProblem(C.Structure):
     _fields_ = [
         ("n_frames", C.c_int), ("victim", C.c_int), ("frame_state", _dp),

@@ -246,6 +246,39 @@ class BaContext:
         check(self._lib.xrhip_ba_debug_linearize(self._h, C.byref(s), _p(H), _p(g), _p(hll), _p(gl), _p(W), C.byref(cost)))
         return dict(H=H, g=g, hll=hll[:Ln], gl=gl[:Ln], W=W[:Ln], cost=cost.value)
 
+    def covariance(self, pd, sel, landmarks=False, prefill=None):
+        """xrhip_ba_covariance at pd's current states: the 15 x 15 marginal covariance blocks (dq dp dv dbg dba) of the frames `sel`
+        and, with landmarks=True, the variance of every landmark's inverse depth.  -> dict(blocks [len(sel)][15][15], var [L] or None,
+        status, rcond).  With status 1 / 2 the outputs are what they were before the call: `prefill` (NaN by default)."""
+        sel = np.ascontiguousarray(sel, np.int32).reshape(-1)
+        fill = np.nan if prefill is None else prefill
+        blocks = np.full((len(sel), 15, 15), fill)
+        var = np.full(max(len(pd.inv_depth), 1), fill) if landmarks else None
+        status = np.full(1, -1, np.int32)
+        rcond = np.zeros(1)
+        s = pd.struct()
+        rq = abi.CovRequest(len(sel), sel.ctypes.data_as(C.POINTER(C.c_int)), blocks.ctypes.data_as(C.POINTER(C.c_double)),
+                            var.ctypes.data_as(C.POINTER(C.c_double)) if landmarks else None,
+                            status.ctypes.data_as(C.POINTER(C.c_int)), rcond.ctypes.data_as(C.POINTER(C.c_double)))
+        self._lib.xrhip_ba_covariance.argtypes = [C.c_void_p, C.POINTER(abi.BaProblem), C.POINTER(abi.CovRequest)]
+        check(self._lib.xrhip_ba_covariance(self._h, C.byref(s), C.byref(rq)))
+        return dict(blocks=blocks, var=var[:len(pd.inv_depth)] if landmarks else None, status=int(status[0]), rcond=float(rcond[0]))
+
+    def stats(self, reset=False):
+        """xrhip_ba_get_stats -> harness.runner.BaStats"""
+        from .harness.runner import BaStats
+        st = BaStats()
+        self._lib.xrhip_ba_get_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        check(self._lib.xrhip_ba_get_stats(self._h, C.byref(st), 1 if reset else 0))
+        return st
+
+    def cov_times(self):
+        """xrhip_ba_debug_cov_times: ms of kc_factor, kc_selected_inverse, kc_landmark_var, the whole call (profiling on)"""
+        out = np.zeros(4)
+        self._lib.xrhip_ba_debug_cov_times.argtypes = [C.c_void_p, C.c_void_p]
+        check(self._lib.xrhip_ba_debug_cov_times(self._h, _p(out)))
+        return out
+
     ROUTES = {0: "none", 1: "tiny", 2: "chain", 3: "small_mid", 4: "multi"}
 
     def debug_last_route(self):

@@ -8,6 +8,8 @@
 #include "ba_chain.hip.h"
 #include "ba_plan.hpp"
 #include "marg_kernels.hip.h"
+#include "cov_kernels.hip.h"
+#include "host/covariance.hpp"
 #include "common.hip.h"
 #include "group.hip.h"
 
@@ -126,7 +128,11 @@ struct xrhip_ba {
     };
     std::vector<TimedChain> pending_chain;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
-    xrhip_ba_stats stats = {0, 0, 0.0, 0, 0.0, 0, 0, 0.0, 0.0};
+    xrhip_ba_stats stats = {0, 0, 0.0, 0, 0.0, 0, 0, 0.0, 0.0, 0};
+    char *cov_dev = nullptr;   // scratch of xrhip_ba_covariance (allocated by its first call, grown on demand)
+    size_t cov_cap = 0;
+    hipEvent_t cov_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    double cov_ms[4] = {0.0, 0.0, 0.0, 0.0};
     const TinyArgs *tiny_args = nullptr;   // device address of the staged argument block (kb_tiny)
     // speculative linearisation of window solves (spec_state_block): second stream, second set of linearisation buffers
     hipStream_t stream2 = nullptr;
@@ -649,6 +655,8 @@ static void launch_linearize(xrhip_ba *c, const BaDims &d, const SolvePlan &pl, 
     else hipLaunchKernelGGL(kb_sum_cost, dim3(1), dim3(256), 0, s, d, p);
 }
 
+constexpr int LINEARIZE_LAUNCHES = 4;   // of launch_linearize with for_solver == false: kb_lin_all, kb_landmark_vision, kb_assemble, kb_sum_cost
+
 static void launch_schur_aux(const BaDims &d, const BaPtrs &p, hipStream_t s) {
     hipLaunchKernelGGL(kb_schur_aux, dim3(schur_aux_blocks(d)), dim3(256), 0, s, d, p);
 }
@@ -787,7 +795,7 @@ int xrhip_ba_get_stats(xrhip_ba *c, xrhip_ba_stats *out, int reset) {
     if (!c || !out) return xr_fail(XRHIP_EINVAL, "xrhip_ba_get_stats: null argument");
     ba_resolve_pending(c);
     *out = c->stats;
-    if (reset) c->stats = {0, 0, 0.0, 0, 0.0, 0, 0, 0.0, 0.0};
+    if (reset) c->stats = {0, 0, 0.0, 0, 0.0, 0, 0, 0.0, 0.0, 0};
     return XRHIP_OK;
 }
 
@@ -869,6 +877,9 @@ void xrhip_ba_destroy(xrhip_ba *c) {
     if (std::getenv("XRHIP_HOSTPROF") && c->spec_launched)
         std::fprintf(stderr, "[hostprof] speculative linearisations: %ld launched, %ld taken\n", c->spec_launched, c->spec_taken);
     hipFree(c->work_spec);
+    hipFree(c->cov_dev);
+    for (hipEvent_t e : c->cov_ev)
+        if (e) hipEventDestroy(e);
     if (c->ev_mid) hipEventDestroy(c->ev_mid);
     if (c->ev_marg) hipEventDestroy(c->ev_marg);
     if (c->ev_spec) hipEventDestroy(c->ev_spec);
@@ -1445,6 +1456,152 @@ int xrhip_ba_debug_linearize(xrhip_ba *c, const xrhip_ba_problem *P, double *H, 
         for (int l = 0; l < d.L; ++l)
             for (int a = 0; a < 6 * d.F; ++a) W[(size_t)l * 6 * d.F + a] = wt[(size_t)l * d.PF + a];
     if (cost) *cost = c->h_ctl->x_cost;
+    return XRHIP_OK;
+}
+
+/* Marginal covariance of selected frames' states and of the landmarks' inverse depths at the problem's current states (DESIGN.md
+ * 4.15; kernels in cov_kernels.hip.h).  One linearisation and the Schur product as the solve launches them, then launches of its
+ * own on the context's stream; nothing of the solve's state on the context is read or kept. */
+int xrhip_ba_covariance(xrhip_ba *c, const xrhip_ba_problem *P, const xrhip_cov_request *req) {
+    if (!c) return xr_fail(XRHIP_EINVAL, "xrhip_ba_covariance: null context");
+    if (c->begun.active) return xr_fail(XRHIP_ESTATE, "xrhip_ba_covariance: a solve begun on this context has not been collected (xrhip_ba_solve_end)");
+    int rc = validate(P);
+    if (rc) return rc;
+    int na = 0;
+    if (const char *why = xrh::covariance_check_request(req, P->n_frames, P->frame_fix, &na)) {
+        std::snprintf(xr_err_buf(), 512, "xrhip_ba_covariance: %s", why);
+        return XRHIP_EINVAL;
+    }
+    std::vector<int> act_inv((size_t)15 * P->n_frames, -1);
+    for (int a = 0, i = 0; a < 15 * P->n_frames; ++a) {
+        const int f = a / 15, k = a % 15;
+        if (k < 6 ? !(P->frame_fix[f] & XRHIP_FIX_POSE) : !(P->frame_fix[f] & XRHIP_FIX_MOTION)) act_inv[a] = i++;
+    }
+    if (req->rcond_estimate) *req->rcond_estimate = 0.0;
+    if (na == 0) {
+        *req->status = 2;
+        return XRHIP_OK;
+    }
+    BaDims d;
+    SolvePlan pl;
+    BaPtrs p;
+    Ext cam, imu;
+    rc = stage_problem(c, P, d, pl, p, cam, imu);
+    if (rc) return rc;
+    d.schur_mode = 0;   // the covariance's Schur product is f64 whatever study mode the context was left in (xrhip_ba_debug_set_schur_precision)
+    const bool want_var = req->out_inv_depth_var && d.L > 0;
+    const bool full = want_var && d.nla > 0;   // every landmark constant: all variances are 0, nothing to launch for them
+    const int n16 = round_up(na, 16), nt = n16 / 16, n_sel = req->n_sel;
+    constexpr int SEL_BATCH = 64;   // selected frames per kc_selected_inverse launch (bounds the right-hand-side scratch: <= 7.9 MB)
+    const int groups = std::max(full ? nt : 0, std::min(n_sel, SEL_BATCH));   // (nt <= 60)
+    // ---- scratch
+    size_t w = 0;
+    auto carve = [&](size_t bytes) {
+        size_t off = (w + 255) & ~size_t(255);
+        w = off + std::max(bytes, size_t(8));
+        return off;
+    };
+    const size_t D8 = sizeof(double);
+    const size_t o_st = carve(sizeof(CovStatus)), o_A = carve(D8 * (size_t)n16 * n16), o_Li = carve(D8 * 256 * (size_t)nt), o_ds = carve(D8 * n16);
+    const size_t o_cols = carve(sizeof(int) * 16 * (size_t)(n_sel + nt)), o_B = carve(D8 * 16 * (size_t)n16 * std::max(groups, 1));
+    const size_t o_Sig = carve(full ? D8 * (size_t)n16 * n16 : 8), o_out = carve(D8 * 225 * (size_t)std::max(n_sel, 1)), o_var = carve(D8 * std::max(d.L, 1));
+    if (w + 256 > c->cov_cap) {
+        XR_HIP(hipStreamSynchronize(c->stream));
+        if (c->cov_dev) hipFree(c->cov_dev);
+        c->cov_dev = nullptr;
+        c->cov_cap = 0;
+        const size_t cap = std::max((w + 256) * 2, size_t(1) << 20);
+        XR_HIP(hipMalloc(&c->cov_dev, cap));
+        c->cov_cap = cap;
+    }
+    char *S = c->cov_dev;
+    CovStatus *st = (CovStatus *)(S + o_st);
+    double *A = (double *)(S + o_A), *Li = (double *)(S + o_Li), *ds = (double *)(S + o_ds), *B = (double *)(S + o_B);
+    double *Sig = (double *)(S + o_Sig), *dout = (double *)(S + o_out), *dvar = (double *)(S + o_var);
+    int *dcols = (int *)(S + o_cols);
+    // column lists: one group of 16 per selected frame (its 15 dofs), then -- full inverse -- one per tile column
+    std::vector<int> cols(16 * (size_t)(n_sel + nt), -1);
+    for (int k = 0; k < n_sel; ++k)
+        for (int q = 0; q < 15; ++q) cols[16 * (size_t)k + q] = act_inv[15 * req->sel_frames[k] + q];
+    for (int t = 0; t < nt; ++t)
+        for (int q = 0; q < 16; ++q) cols[16 * (size_t)(n_sel + t) + q] = (16 * t + q < na) ? 16 * t + q : -1;
+    hipStream_t s = c->stream;
+    const bool timed = c->profiling;
+    if (timed)
+        for (hipEvent_t &e : c->cov_ev)
+            if (!e) XR_HIP(hipEventCreate(&e));
+    long launches = 1;   // kb_stage (stage_problem)
+    XR_HIP(hipMemsetAsync(st, 0, sizeof(CovStatus), s));
+    XR_HIP(hipMemcpyAsync(dcols, cols.data(), sizeof(int) * cols.size(), hipMemcpyHostToDevice, s));
+    if (timed) XR_HIP(hipEventRecord(c->cov_ev[0], s));
+    // ---- the linearisation and the Schur product, as they are
+    if (d.np) {
+        hipLaunchKernelGGL(kb_prior_lambda, dim3(((d.np + 15) / 16) * ((d.np + 15) / 16 + 1)), dim3(256), 0, s, d.np, p.pS, p.pLam, p.pinfo, p.pc0);
+        ++launches;
+    }
+    launch_linearize(c, d, pl, p, cam, imu, P->sqrt_inv_cov[0], P->sqrt_inv_cov[1], false);
+    launches += LINEARIZE_LAUNCHES;
+    if (d.nla) {
+        hipLaunchKernelGGL(kc_weights, dim3((d.L + 255) / 256), dim3(256), 0, s, d.L, p.lact, p.hll, p.omega);
+        const int tiles = d.PF / 16;
+        hipLaunchKernelGGL(kb_schur_mfma, dim3(tiles * tiles), dim3(256), 0, s, d, p);
+        launches += 2;
+    }
+    // ---- compaction, factorisation, substitutions
+    hipLaunchKernelGGL(kc_compact, dim3((unsigned)(((size_t)n16 * n16 + 255) / 256)), dim3(256), 0, s, d, p, n16, A, ds);
+    if (timed) XR_HIP(hipEventRecord(c->cov_ev[1], s));
+    hipLaunchKernelGGL(kc_factor, dim3(1), dim3(COV_NT), 0, s, na, n16, A, Li, st);
+    if (timed) XR_HIP(hipEventRecord(c->cov_ev[2], s));
+    launches += 2;
+    if (full) {
+        hipLaunchKernelGGL(kc_selected_inverse, dim3(nt), dim3(256), 0, s, na, n16, A, Li, ds, dcols + 16 * (size_t)n_sel, B, 1, Sig, st);
+        ++launches;
+        if (n_sel) {
+            hipLaunchKernelGGL(kc_gather_blocks, dim3(n_sel), dim3(256), 0, s, n16, Sig, dcols, dout, st);
+            ++launches;
+        }
+    } else {
+        for (int base = 0; base < n_sel; base += SEL_BATCH) {   // (stream order: a batch reuses B after the one before it)
+            hipLaunchKernelGGL(kc_selected_inverse, dim3(std::min(SEL_BATCH, n_sel - base)), dim3(256), 0, s, na, n16, A, Li, ds,
+                               dcols + 16 * (size_t)base, B, 0, dout + 225 * (size_t)base, st);
+            ++launches;
+        }
+    }
+    if (timed) XR_HIP(hipEventRecord(c->cov_ev[3], s));
+    if (full) {
+        hipLaunchKernelGGL(kc_landmark_var, dim3((d.L + 3) / 4), dim3(64), 0, s, d, p, n16, Sig, dvar, st);
+        ++launches;
+    }
+    if (timed) XR_HIP(hipEventRecord(c->cov_ev[4], s));
+    XR_HIP(hipGetLastError());
+    c->stats.n_cov_launches += launches;
+    CovStatus hst;
+    XR_HIP(hipMemcpyAsync(&hst, st, sizeof(CovStatus), hipMemcpyDeviceToHost, s));
+    XR_HIP(hipStreamSynchronize(s));
+    *req->status = hst.status ? 1 : 0;
+    if (hst.status) {
+        std::snprintf(xr_err_buf(), 512, "xrhip_ba_covariance: pivot %d of %d is not positive to working precision (status 1)", hst.pivot, na);
+        return XRHIP_OK;
+    }
+    if (req->rcond_estimate) *req->rcond_estimate = hst.max_pivot > 0.0 ? hst.min_pivot / hst.max_pivot : 0.0;
+    if (n_sel) XR_HIP(hipMemcpyAsync(req->out_blocks, dout, D8 * 225 * (size_t)n_sel, hipMemcpyDeviceToHost, s));
+    if (full) XR_HIP(hipMemcpyAsync(req->out_inv_depth_var, dvar, D8 * d.L, hipMemcpyDeviceToHost, s));
+    XR_HIP(hipStreamSynchronize(s));
+    if (want_var && !full) std::memset(req->out_inv_depth_var, 0, D8 * d.L);
+    if (timed) {
+        float ms = 0.f;
+        for (int k = 0; k < 4; ++k) {
+            const int a = k == 3 ? 0 : k + 1, b = k == 3 ? 4 : k + 2;
+            c->cov_ms[k] = hipEventElapsedTime(&ms, c->cov_ev[a], c->cov_ev[b]) == hipSuccess ? ms : 0.0;
+        }
+        if (!full) c->cov_ms[2] = 0.0;
+    }
+    return XRHIP_OK;
+}
+
+int xrhip_ba_debug_cov_times(xrhip_ba *c, double *ms4) {
+    if (!c || !ms4) return xr_fail(XRHIP_EINVAL, "xrhip_ba_debug_cov_times: null argument");
+    std::memcpy(ms4, c->cov_ms, sizeof(c->cov_ms));
     return XRHIP_OK;
 }
 

@@ -40,6 +40,7 @@
 #include "../hostprof.hpp"
 #include "ba_dump.hpp"
 #include "config.hpp"
+#include "covariance.hpp"
 #include "map.hpp"
 #include "parsac.hpp"
 #include "pixel_format.hpp"
@@ -64,6 +65,8 @@ int xrhip_image_render_view(xrhip_image *img, const xrhip_view_segment *segs, in
 // (likewise the Lucas-Kanade parameters: a library without the entry point tracks with the reference's constants, which is all the
 // configuration may then ask for -- Pipeline::apply_lk_params)
 int xrhip_klt_set_lk_params(xrhip_klt *ctx, const xrhip_lk_params *p) __attribute__((weak));
+// (likewise the covariance of a solved window: a library without it answers status -1 -- BaBuilder::covariance)
+int xrhip_ba_covariance(xrhip_ba *ctx, const xrhip_ba_problem *problem, const xrhip_cov_request *req) __attribute__((weak));
 }
 
 namespace xrh {
@@ -228,6 +231,17 @@ struct Pipeline {
     std::vector<xrhip_image *> image_pool;
     double noise36[36];
     StageTimes times;
+    // XRSLAMAmdSetCovariance: the covariance of the newest keyframe after the last window solve (BaBuilder::covariance), kept until
+    // the next one.  status -1: none yet, or the library behind xrslam_hip.h has no xrhip_ba_covariance (`error` says so).
+    struct Covariance {
+        bool enabled = false;
+        double t = 0.0;
+        double state[225] = {0.0};
+        int status = -1;
+        double rcond = 0.0;
+        std::vector<std::pair<long long, double>> landmark_var;   // (track id, variance of its inverse depth): the solve's free landmarks
+        std::string error;
+    } cov;
     unsigned long ba_generation = 0;   // BaBuilder instances stamp frames / tracks with it
     bool undistort_on_device = false;  // frames arrive as the camera recorded them; the KLT context holds the inverse map
     // cv::undistort / ImageUndistorter on the device from now on (model: "cv_undistort", "radtan", "equidistant"), or off (nullptr)
@@ -1032,6 +1046,35 @@ class BaBuilder {
             hip_check(xrhip_ba_solve(P_.ba, &pb_, &sm), "xrhip_ba_solve");
         }
         return finish(sm, elapsed_device_ms);
+    }
+    // After solve(): the marginal covariance of frame `f` (a frame of this problem) and the variances of the landmarks' inverse depths at
+    // the solved states, into Pipeline::cov (XRSLAMAmdSetCovariance).  A reported condition (status 1 / 2) is kept as the answer; a
+    // library without xrhip_ba_covariance answers status -1.
+    void covariance(Frame *f) {
+        Pipeline::Covariance &cv = P_.cov;
+        cv.t = f->image ? f->image->t : 0.0;
+        cv.landmark_var.clear();
+        cv.rcond = 0.0;
+        std::fill(cv.state, cv.state + 225, 0.0);
+        if (!xrhip_ba_covariance) {
+            cv.status = -1;
+            cv.error = "XRSLAMAmdSetCovariance: this library has no xrhip_ba_covariance";
+            return;
+        }
+        if (!prepared_ || f->ba_gen != gen_) throw std::logic_error("covariance: the frame is not part of the solved problem");
+        const int sel = f->ba_index, L = (int)tracks_.size();
+        std::vector<double> var(std::max(L, 1), 0.0);
+        int status = -1;
+        const xrhip_cov_request rq = {1, &sel, cv.state, var.data(), &status, &cv.rcond};
+        hip_check(xrhip_ba_covariance(P_.ba, &pb_, &rq), "xrhip_ba_covariance");
+        cv.status = status;
+        cv.error.clear();
+        if (status != 0) {
+            std::fill(cv.state, cv.state + 225, 0.0);
+            return;
+        }
+        for (int l = 0; l < L; ++l)
+            if (!lfix_[l] && var[l] > 0.0) cv.landmark_var.emplace_back((long long)tracks_[l]->id, var[l]);
     }
     // Two problems in one go (xrhip_ba_solve_chained): `second` contains frame `link`, which `first` optimises; it starts from the
     // first solve's result for that frame (on the device: one submission, one wait for the pair).  Both builders must be prepared
@@ -2064,6 +2107,7 @@ class SlidingWindowTracker {
             P_.integrate_batch_end();
         }
         b.solve();
+        if (P_.cov.enabled) b.covariance(map->get_frame(map->frame_num() - 1));
         xrhip::HostProfScope hp_c(19, "refine_window: landmark sweep");
         const bool log_cull = P_.swt_log.enabled();
         std::vector<std::pair<const Frame *, PoseState>> cam_cache;

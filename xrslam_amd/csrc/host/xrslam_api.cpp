@@ -373,6 +373,51 @@ void impl_get_ba_stats(Manager &m, void *out, int reset) {
     });
 }
 
+void impl_set_covariance(Manager &m, int enable) {
+    if (!m.sys) return;
+    impl_flush(m);   // pipelined mode: the backend thread reads the switch
+    m.sys->P.cov.enabled = enable != 0;
+}
+
+int impl_get_covariance(Manager &m, XRSLAMAmdCovariance *out) {
+    if (!out) return 0;
+    std::memset(out, 0, sizeof(*out));
+    out->status = -1;
+    if (!m.sys) return 0;
+    impl_flush(m);
+    const xrh::Pipeline::Covariance &cv = m.sys->P.cov;
+    out->timestamp = cv.t;
+    out->status = cv.status;
+    out->rcond_estimate = cv.rcond;
+    std::memcpy(out->state, cv.state, sizeof(cv.state));
+    xrh::covariance_pose_ros(cv.state, &out->pose_ros[0][0]);
+    if (cv.status == -1 && !cv.error.empty()) m.last_error = cv.error;
+    return cv.status == 0 ? 1 : 0;
+}
+
+int impl_get_landmark_variances(Manager &m, double *var, long long *ids, int cap) {
+    if (!m.sys) return 0;
+    impl_flush(m);
+    int n = 0;
+    guarded(m, [&] {
+        if (!m.sys->swt || m.sys->P.cov.status != 0) return;
+        xrh::Map *map = m.sys->swt->map.get();
+        std::vector<long long> valid;
+        for (size_t i = 0; i < map->track_num(); ++i)
+            if (map->get_track(i)->tag(xrh::TT_VALID)) valid.push_back((long long)map->get_track(i)->id);
+        std::sort(valid.begin(), valid.end());
+        for (const auto &[id, v] : m.sys->P.cov.landmark_var) {
+            if (!std::binary_search(valid.begin(), valid.end(), id)) continue;
+            if (n < cap) {
+                if (var) var[n] = v;
+                if (ids) ids[n] = id;
+            }
+            ++n;
+        }
+    });
+    return n;
+}
+
 void impl_get_klt_stats(Manager &m, void *out, int reset) {
     if (!m.sys || !out) return;
     bind_device(m);
@@ -516,6 +561,9 @@ void XRSLAMAmdGetTimes(XRSLAMAmdTimes *out) { impl_get_times(mgr(), out); }
 void XRSLAMAmdSetProfiling(int enable) { impl_set_profiling(mgr(), enable); }
 void XRSLAMAmdGetBaStats(void *out, int reset) { impl_get_ba_stats(mgr(), out, reset); }
 void XRSLAMAmdGetKltStats(void *out, int reset) { impl_get_klt_stats(mgr(), out, reset); }
+void XRSLAMAmdSetCovariance(int enable) { impl_set_covariance(mgr(), enable); }
+int XRSLAMAmdGetCovariance(XRSLAMAmdCovariance *out) { return impl_get_covariance(mgr(), out); }
+int XRSLAMAmdGetLandmarkVariances(double *var, long long *ids, int cap) { return impl_get_landmark_variances(mgr(), var, ids, cap); }
 void XRSLAMAmdGetInitReport(XRSLAMAmdInitReport *out) { impl_get_init_report(mgr(), out); }
 int XRSLAMAmdGetTrackerParams(XRSLAMAmdTrackerParams *out) { return impl_get_tracker_params(mgr(), out); }
 const char *XRSLAMAmdLastError(void) { return mgr().last_error.c_str(); }
@@ -602,6 +650,20 @@ void XRSLAMAmdInstanceGetInitReport(XRSLAMAmdInstance *inst, XRSLAMAmdInitReport
 }
 int XRSLAMAmdInstanceGetTrackerParams(XRSLAMAmdInstance *inst, XRSLAMAmdTrackerParams *out) {
     return inst ? impl_get_tracker_params(inst->m, out) : 0;
+}
+void XRSLAMAmdInstanceSetCovariance(XRSLAMAmdInstance *inst, int enable) {
+    if (inst) impl_set_covariance(inst->m, enable);
+}
+int XRSLAMAmdInstanceGetCovariance(XRSLAMAmdInstance *inst, XRSLAMAmdCovariance *out) {
+    if (inst) return impl_get_covariance(inst->m, out);
+    if (out) {
+        std::memset(out, 0, sizeof(*out));
+        out->status = -1;
+    }
+    return 0;
+}
+int XRSLAMAmdInstanceGetLandmarkVariances(XRSLAMAmdInstance *inst, double *var, long long *ids, int cap) {
+    return inst ? impl_get_landmark_variances(inst->m, var, ids, cap) : 0;
 }
 const char *XRSLAMAmdInstanceLastError(XRSLAMAmdInstance *inst) { return inst ? inst->m.last_error.c_str() : ""; }
 void XRSLAMAmdInstanceSetThreading(XRSLAMAmdInstance *inst, int mode) {

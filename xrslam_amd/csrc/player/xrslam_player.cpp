@@ -7,7 +7,7 @@
 //
 //   xrslam-player --slam configs/euroc_slam.yaml --device configs/euroc_sensor.yaml --euroc <dir>/mav0
 //                 [--out traj.tum] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined]
-//                 [--push-color] [--push-format gray16|rgb|rgba] [--push-scaled]
+//                 [--push-color] [--push-format gray16|rgb|rgba] [--push-scaled] [--cov-out FILE]
 //
 // (--push-color: a colour PNG is pushed as BGR / BGRA with channel 3 / 4 and reduced to gray by the library instead of by the reader.)
 // (--push-scaled: a PNG larger than cam0.resolution is pushed at its own size, the whole frame as the crop, and cropped / area-scaled
@@ -103,7 +103,7 @@ int main(int argc, char **argv) {
     if (!opt.count("slam") || !opt.count("device") || !opt.count("euroc")) {
         std::fprintf(stderr, "usage: xrslam-player --slam cfg.yaml --device sensor.yaml --euroc <dir>/mav0 [--out traj.tum] "
                              "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color] [--push-format gray16|rgb|rgba] [--push-scaled]\n"
-                             "       [--view-out DIR [--view-every N] [--view-mode reference|age] [--view-trail K]]\n"
+                             "       [--cov-out FILE] [--view-out DIR [--view-every N] [--view-mode reference|age] [--view-trail K]]\n"
                              "   or: xrslam-player -sc cfg.yaml -dc sensor.yaml [--tum traj.tum] [--csv traj.csv] [-p] "
                              "euroc://<dir>/mav0 | tum://<dir>/mav0\n");
         return 2;
@@ -151,7 +151,10 @@ int main(int argc, char **argv) {
     }
     FILE *out = opt.count("out") ? std::fopen(opt["out"].c_str(), "w") : nullptr;
     FILE *csv = opt.count("csv") ? std::fopen(opt["csv"].c_str(), "w") : nullptr;
-    if ((opt.count("out") && !out) || (opt.count("csv") && !csv)) {
+    // --cov-out FILE: one line per answered frame -- timestamp of the covariance, the 21 upper-triangle entries of pose_ros, status
+    FILE *cov = opt.count("cov-out") ? std::fopen(opt["cov-out"].c_str(), "w") : nullptr;
+    if (cov) XRSLAMAmdSetCovariance(1);
+    if ((opt.count("out") && !out) || (opt.count("csv") && !csv) || (opt.count("cov-out") && !cov)) {
         std::fprintf(stderr, "Cannot open file\n");   // trajectory_writer.h:37,62
         return 1;
     }
@@ -302,6 +305,14 @@ int main(int argc, char **argv) {
                         ++tracked;
                         if (out) write_tum_pose(out, pose.timestamp, pose.translation, pose.quaternion);
                         if (csv) write_csv_pose(csv, pose.timestamp, pose.translation, pose.quaternion);
+                        if (cov) {
+                            XRSLAMAmdCovariance cv;
+                            XRSLAMAmdGetCovariance(&cv);
+                            std::fprintf(cov, "%.9f", cv.timestamp);
+                            for (int i = 0; i < 6; ++i)
+                                for (int j = i; j < 6; ++j) std::fprintf(cov, " %.17g", cv.pose_ros[i][j]);
+                            std::fprintf(cov, " %d\n", cv.status);
+                        }
                         if (const TruthRow *g = nearest_truth(gt, pose.timestamp, 2.6e-3)) {
                             est.push_back({pose.translation[0], pose.translation[1], pose.translation[2]});
                             ref.push_back({g->p[0], g->p[1], g->p[2]});
@@ -316,6 +327,7 @@ int main(int argc, char **argv) {
     const double busy = std::chrono::duration<double>(std::chrono::steady_clock::now() - loop_begin).count() - io_seconds;
     if (out) std::fclose(out);
     if (csv) std::fclose(csv);
+    if (cov) std::fclose(cov);
     if (!view_failed && !write_view()) view_failed = true;
     const char *err = XRSLAMAmdLastError();
     if (view_failed && !(err && *err)) err = "the tracking view could not be written";

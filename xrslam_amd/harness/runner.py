@@ -27,7 +27,12 @@ class XRSLAMPose(C.Structure):
 class BaStats(C.Structure):   # xrhip_ba_stats (include/xrslam_hip.h)
     _fields_ = [("n_solve_try", C.c_long), ("n_trials", C.c_long), ("ms_solve_try", C.c_double), ("n_timed", C.c_long),
                 ("flops_solve_try", C.c_double), ("n_tiny", C.c_long), ("n_chain_timed", C.c_long), ("ms_chain", C.c_double),
-                ("bytes_chain", C.c_double)]
+                ("bytes_chain", C.c_double), ("n_cov_launches", C.c_long)]
+
+
+class XRSLAMAmdCovariance(C.Structure):   # include/XRSLAM.h
+    _fields_ = [("timestamp", C.c_double), ("state", (C.c_double * 15) * 15), ("pose_ros", (C.c_double * 6) * 6), ("status", C.c_int),
+                ("rcond_estimate", C.c_double)]
 
 
 class XRSLAMAmdTimes(C.Structure):
@@ -141,6 +146,12 @@ def load(lib_path):
     lib.XRSLAMAmdSetThreading.argtypes = [C.c_int]
     lib.XRSLAMAmdSetThreading.restype = None
     lib.XRSLAMAmdFlush.restype = None
+    have_cov = hasattr(lib, "XRSLAMAmdGetCovariance")
+    if have_cov:   # covariance of the newest keyframe / landmark variances
+        lib.XRSLAMAmdSetCovariance.argtypes = [C.c_int]
+        lib.XRSLAMAmdSetCovariance.restype = None
+        lib.XRSLAMAmdGetCovariance.argtypes = [C.POINTER(XRSLAMAmdCovariance)]
+        lib.XRSLAMAmdGetLandmarkVariances.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     have_view = hasattr(lib, "XRSLAMAmdRenderTrackingView")
     if have_view:   # the tracking view (feature snapshot + rendered overlay)
         lib.XRSLAMAmdGetFeatures.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
@@ -162,6 +173,11 @@ def load(lib_path):
             fn = getattr(lib, "XRSLAMAmdInstance" + name)
             fn.argtypes = [H] + args
             fn.restype = res
+        if have_cov:
+            lib.XRSLAMAmdInstanceSetCovariance.argtypes = [H, C.c_int]
+            lib.XRSLAMAmdInstanceSetCovariance.restype = None
+            lib.XRSLAMAmdInstanceGetCovariance.argtypes = [H, C.POINTER(XRSLAMAmdCovariance)]
+            lib.XRSLAMAmdInstanceGetLandmarkVariances.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int]
         if have_view:
             lib.XRSLAMAmdInstanceGetFeatures.argtypes = [H, C.c_void_p, C.c_int, C.POINTER(C.c_double)]
             lib.XRSLAMAmdInstanceSetFeatureHistory.argtypes = [H, C.c_int]
@@ -255,6 +271,10 @@ class _Api:
             names["push_image_format"] = ("XRSLAMAmdPushImageFormat", "XRSLAMAmdInstancePushImageFormat")
         if hasattr(lib, "XRSLAMAmdPushImageScaled"):
             names["push_image_scaled"] = ("XRSLAMAmdPushImageScaled", "XRSLAMAmdInstancePushImageScaled")
+        if hasattr(lib, "XRSLAMAmdGetCovariance"):
+            names["set_covariance"] = ("XRSLAMAmdSetCovariance", "XRSLAMAmdInstanceSetCovariance")
+            names["get_covariance"] = ("XRSLAMAmdGetCovariance", "XRSLAMAmdInstanceGetCovariance")
+            names["get_landmark_variances"] = ("XRSLAMAmdGetLandmarkVariances", "XRSLAMAmdInstanceGetLandmarkVariances")
         if hasattr(lib, "XRSLAMAmdRenderTrackingView"):
             names["get_features"] = ("XRSLAMAmdGetFeatures", "XRSLAMAmdInstanceGetFeatures")
             names["set_feature_history"] = ("XRSLAMAmdSetFeatureHistory", "XRSLAMAmdInstanceSetFeatureHistory")
@@ -431,6 +451,24 @@ class Session:
         st = BaStats()
         self.api.get_ba_stats(C.byref(st), 1 if reset else 0)
         return st
+
+    def set_covariance(self, on):
+        """XRSLAMAmdSetCovariance: every window solve is followed by the covariance of its newest keyframe"""
+        self.api.set_covariance(1 if on else 0)
+
+    def covariance(self):
+        """-> (available, XRSLAMAmdCovariance): timestamp, state [15][15], pose_ros [6][6], status, rcond_estimate"""
+        out = XRSLAMAmdCovariance()
+        ok = self.api.get_covariance(C.byref(out))
+        return ok == 1, out
+
+    def landmark_variances(self):
+        """-> (variances of the inverse depths, track ids) of the last window solve's free landmarks that are still valid"""
+        n = self.api.get_landmark_variances(None, None, 0)
+        var, ids = np.zeros(n), np.zeros(n, np.int64)
+        if n:
+            assert self.api.get_landmark_variances(var.ctypes.data, ids.ctypes.data, n) == n
+        return var, ids
 
     def set_feature_history(self, frames):
         """Trail history of the feature snapshot, 0 .. 8 frames (XRSLAMAmdSetFeatureHistory)"""
