@@ -1,19 +1,65 @@
-"""Reference of the covariance tests (xrhip_ba_covariance): the cases, the reference inverse, a second CPU evaluation of it, and the
-tolerance that follows from the two.
+"""Reference of the covariance tests (xrhip_ba_covariance): the cases, the reference inverse, a second CPU evaluation of it, the
+tolerance that follows from the two, and -- for the small cases -- the same quantities at 50 digits.
 
 Reference: the oracle's dense H over all free dofs (orc_ba_linearize), Sigma_ref = np.linalg.inv(H), read through the returned
 offsets.  Second evaluation: the Jacobi-scaled Schur complement of the same H in numpy, cholesky, triangular solves -- the route the
 device takes, in LAPACK's summation order.  d_ref is the test's metric between the two; a case's tolerance is max(1e-9, 50 d_ref):
 the error of either evaluation scales with the system's condition number, and the factor 50 covers the different summation order of
-the matrix-core tiles.  Everything is computed once per case and cached; nobody modifies what is returned."""
+the matrix-core tiles.  Everything is computed once per case and cached; nobody modifies what is returned.
+
+reference_hp: the Cholesky factor of the same H in mpmath at 50 digits (landmarks ordered first, so the trailing block of the factor
+is the factor of the reduced system), the covariance entries from it rounded to doubles, and the pivots of the Jacobi-scaled reduced
+system.  Only where the order of H is <= about 130 (HP_CASES): a second or two per case.
+
+The case lists:
+  CASES           parity of every frame's block against np.linalg.inv (the large cases end at the cap: na = 960 = n16)
+  PARTIAL_CASES   frames with FIX_POSE or FIX_MOTION alone (-1 slots inside a frame's column group; na = 75, 84, 54)
+  EDGE_CASES      landmark edges of kc_landmark_var (L % 4 = 1, 2, 3; a landmark seen by constant frames only)
+  ILL_CASES       one window (K = 6, L = 12) with a progressively weaker gauge prior: cond(scaled S) 5e8 ... 1e14
+"""
 import functools
 
 import numpy as np
 
 from xrslam_amd import abi
 
-CASES = ("k2_fix0", "k3_prior", "k3_l1", "k3_l5", "k6", "k11", "k16", "k21", "k36_l40", "s1_window", "s2_window", "s3_window", "localize")
-LANDMARK_CASES = ("k3_l1", "k3_l5", "k11", "s1_window")
+SMALL_CASES = ("k2_fix0", "k3_prior", "k3_l1", "k3_l5", "k6", "k11", "k16", "k21", "k36_l40", "s1_window", "s2_window", "s3_window", "localize")
+LARGE_CASES = ("k40_l60", "k49", "k64_fix0", "k64")
+CASES = SMALL_CASES + LARGE_CASES
+LANDMARK_CASES = ("k3_l1", "k3_l5", "k11", "s1_window", "s3_window", "k64_fix0", "k64")
+PARTIAL_CASES = ("k6_mixed", "k6_fixpose0", "k5_straddle")
+EDGE_CASES = ("edge_l9", "edge_l10", "edge_l11")
+ILL_CASES = ("ill_5e8", "ill_1e10", "ill_1e12", "ill_7e12", "ill_1e14")
+HP_CASES = ("k2_fix0", "k3_prior", "k3_l1", "k3_l5", "k6", "localize") + PARTIAL_CASES + EDGE_CASES + ILL_CASES
+TABLE_CASES = CASES + PARTIAL_CASES + EDGE_CASES + ILL_CASES
+
+# What the CPU computed for the new cases when they were chosen (tests/test_cov_model.py holds each to it): na, n16, free landmarks and
+# a band of cond(scaled S) -- a factor of 3 either side of the value found.
+#   k5_straddle: K = 5, frame 1 FIX_MOTION (its free dofs are reduced rows 15..20, across the tile boundary at 16), frames 2 and 3 FIX_POSE
+#   (rows 21..29 and 30..38, the latter across 32); chosen from the fix patterns of K = 4, 5 in which one frame of either kind straddles.
+#   ill_*: the gauge rows of make_window's prior (1e15) scaled to 1e15, 1, 0.1, 0.04, 0.01; cond goes as the inverse square.
+EXPECTED = {
+    "k40_l60": (600, 608, 60, 3.2e5), "k49": (735, 736, 40, 3.4e5), "k64_fix0": (945, 960, 40, 1.7e5), "k64": (960, 960, 40, 3.6e5),
+    "k6_mixed": (75, 80, 39, 2.7e2), "k6_fixpose0": (84, 96, 39, 1.1e8), "k5_straddle": (54, 64, 29, 4.4e1),
+    "edge_l9": (45, 48, 9, 6.0e2), "edge_l10": (45, 48, 9, 5.9e2), "edge_l11": (45, 48, 10, 6.0e2),
+    "ill_5e8": (90, 96, 12, 4.9e8), "ill_1e10": (90, 96, 12, 1.07e10), "ill_1e12": (90, 96, 12, 1.07e12), "ill_7e12": (90, 96, 12, 6.7e12),
+    "ill_1e14": (90, 96, 12, 1.07e14),
+}
+ILL_SCALE = {"ill_5e8": 1.0, "ill_1e10": 1e-15, "ill_1e12": 1e-16, "ill_7e12": 4e-17, "ill_1e14": 1e-17}   # of the prior's sqrt_info
+EDGE_LONELY = 1   # the landmark of the edge cases whose observations are cut down to the constant frames 0 and 1
+
+
+def rebuild(pd, obs_keep=None, imu_keep=None, prior="same", frame_fix=None, landmark_fix=None):
+    """A new BaProblemData from pd's arrays through the constructor (assigning the prior's arrays on an existing one does not reach the
+    C view): a subset of the observations / IMU factors, another prior (a dict, or None), other fix flags."""
+    ok = np.ones(len(pd.obs_tgt), bool) if obs_keep is None else obs_keep
+    ik = np.ones(len(pd.imu_i), bool) if imu_keep is None else imu_keep
+    if isinstance(prior, str):
+        prior = dict(frames=pd.prior_frames, sqrt_info=pd.prior_sqrt_info, infovec=pd.prior_infovec, lin=pd.prior_lin) if len(pd.prior_frames) else None
+    return abi.BaProblemData(pd.frame_state, pd.frame_fix if frame_fix is None else frame_fix, pd.cam_ext, pd.imu_ext, pd.sqrt_inv_cov,
+                             pd.inv_depth, pd.landmark_fix if landmark_fix is None else landmark_fix,
+                             obs=dict(tgt=pd.obs_tgt[ok], ref=pd.obs_ref[ok], lm=pd.obs_lm[ok], z_tgt=pd.obs_z_tgt[ok], z_ref=pd.obs_z_ref[ok]),
+                             imu=dict(i=pd.imu_i[ik], j=pd.imu_j[ik], data=pd.imu_data[ik]), prior=prior, max_iterations=pd.max_iterations)
 
 
 @functools.lru_cache(maxsize=None)
@@ -26,11 +72,40 @@ def problem(name):
         return bs.make_localize()[0]
     if name == "k2_fix0":   # one free frame: na = 15, one tile, every padding path
         return bs.make_window(K=2, L=20, seed=3, with_prior=False, n_fixed_first=1)[0]
+    if name in ("k6_mixed", "k6_fixpose0", "k5_straddle"):
+        K, fix = {"k6_mixed": (6, {2: abi.FIX_MOTION, 4: abi.FIX_POSE}), "k6_fixpose0": (6, {0: abi.FIX_POSE}),
+                  "k5_straddle": (5, {1: abi.FIX_MOTION, 2: abi.FIX_POSE, 3: abi.FIX_POSE})}[name]
+        pd = bs.make_window(K=K, L=40 if K == 6 else 30, seed=11 + K)[0]
+        for f, bits in fix.items():
+            pd.frame_fix[f] = bits
+        return pd
+    if name in ILL_CASES:
+        pd = bs.make_window(K=6, L=12, seed=17)[0]
+        return rebuild(pd, prior=dict(frames=pd.prior_frames, sqrt_info=pd.prior_sqrt_info * ILL_SCALE[name], infovec=pd.prior_infovec, lin=pd.prior_lin))
+    if name in EDGE_CASES:
+        # frames 0 and 1 constant; landmark EDGE_LONELY keeps only the observations among them (its row of W has no free entry); the last
+        # group of four landmarks is short (L % 4 = 1, 2, 3), ends in a free landmark and holds a constant one where it has room for it
+        L = int(name[6:])
+        pd = bs.make_window(K=5, L=L, seed=16, n_fixed_first=2)[0]
+        keep = (pd.obs_lm != EDGE_LONELY) | ((pd.obs_tgt < 2) & (pd.obs_ref < 2))
+        lfix = pd.landmark_fix.copy()
+        if L % 4 >= 2:
+            lfix[L - 2] = 1
+        return rebuild(pd, obs_keep=keep, landmark_fix=lfix)
     # K = 3 with the prior and NOTHING fixed is rank deficient (two IMU intervals do not separate the accelerometer bias from gravity: the
     # smallest eigenvalue of the scaled H is -2e-16), so it cannot be a parity case; the K = 3 cases keep frame 0 constant (na = 30)
     spec = {"k3_prior": (3, 30, 1), "k3_l1": (3, 1, 1), "k3_l5": (3, 5, 1), "k6": (6, 40, 0), "k11": (11, 150, 0), "k16": (16, 60, 0),
-            "k21": (21, 60, 0), "k36_l40": (36, 40, 0)}[name]
+            "k21": (21, 60, 0), "k36_l40": (36, 40, 0), "k40_l60": (40, 60, 0), "k49": (49, 40, 0), "k64_fix0": (64, 40, 1),
+            "k64": (64, 40, 0)}[name]
     return bs.make_window(K=spec[0], L=spec[1], seed=11 + spec[0], n_fixed_first=spec[2])[0]
+
+
+def unanchored_last_frame():
+    """-> a K = 6 window whose last frame is free and touched by no factor: no observation, no IMU factor, and make_window's prior ends
+    at frame K - 2.  The oracle's H has a zero diagonal on that frame's 15 dofs (tests/test_cov_model.py)."""
+    from tests import ba_synth as bs
+    pd = bs.make_window(K=6, L=40, seed=17)[0]
+    return rebuild(pd, obs_keep=(pd.obs_tgt != 5) & (pd.obs_ref != 5), imu_keep=pd.imu_j != 5)
 
 
 def _maps(pd, po, mo):
@@ -56,22 +131,36 @@ def _read(Sig, idx, lo, F):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name):
-    """-> dict(blocks [F][15][15], var [L], blocks2, var2 (the second evaluation), d_blocks [F], d_var [L], cond)"""
+def linearized(name):
+    """-> (H, idx (_maps), lo, fr, lm) of the case: the oracle's normal equations and where the frame dofs and landmarks sit in them"""
     from oracle import ba_oracle as bo
     pd = problem(name)
-    F = len(pd.frame_state)
     _, H, _, po, mo, lo = bo.linearize(pd.copy())
     idx = _maps(pd, po, mo)
+    return H, idx, lo, idx[idx >= 0], np.array([l for l in lo if l >= 0], int)
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    """-> dict(blocks [F][15][15], var [L], blocks2, var2 (the second evaluation; None where numpy's Cholesky of the scaled S fails),
+    d_blocks [F], d_var [L], cond, na, nla, hll [L] (the oracle's diagonal of a free landmark, else 0), piv_min, piv_max (of numpy's
+    factor of the scaled S))"""
+    pd = problem(name)
+    F = len(pd.frame_state)
+    H, idx, lo, fr, lm = linearized(name)
     blocks, var = _read(np.linalg.inv(H), idx, lo, F)
     # second evaluation: Schur complement over the frame dofs, Jacobi scaling, Cholesky, triangular solves
-    fr = idx[idx >= 0]
-    lm = np.array([l for l in lo if l >= 0], int)
     Hpp, hll = H[np.ix_(fr, fr)], np.diag(H)[lm] if len(lm) else np.zeros(0)
     W = H[np.ix_(lm, fr)] if len(lm) else np.zeros((0, len(fr)))
     S = Hpp - W.T @ (W / hll[:, None]) if len(lm) else Hpp
     d = 1.0 / np.sqrt(np.diag(S))
-    Lc = np.linalg.cholesky(S * np.outer(d, d))
+    out = dict(blocks=blocks, var=var, cond=float(np.linalg.cond(S * np.outer(d, d))), na=len(fr), nla=len(lm),
+               hll=np.array([H[l, l] if l >= 0 else 0.0 for l in lo]))
+    try:
+        Lc = np.linalg.cholesky(S * np.outer(d, d))
+    except np.linalg.LinAlgError:
+        out.update(blocks2=None, var2=None, d_blocks=np.full(F, np.inf), d_var=np.full(len(lo), np.inf), piv_min=0.0, piv_max=1.0)
+        return out
     Y = np.linalg.solve(Lc, np.eye(len(fr)))   # (no scipy here: a general solve on the triangular factor)
     Spp = (Y.T @ Y) * np.outer(d, d)
     Sig2 = np.zeros_like(H)
@@ -79,8 +168,71 @@ def reference(name):
     for k, l in enumerate(lm):
         Sig2[l, l] = 1.0 / hll[k] + W[k] @ Spp @ W[k] / hll[k] ** 2
     blocks2, var2 = _read(Sig2, idx, lo, F)
-    return dict(blocks=blocks, var=var, blocks2=blocks2, var2=var2, d_blocks=block_error(blocks2, blocks), d_var=var_error(var2, var),
-                cond=float(np.linalg.cond(S * np.outer(d, d))), na=len(fr), nla=len(lm))
+    piv = np.diag(Lc) ** 2
+    out.update(blocks2=blocks2, var2=var2, d_blocks=block_error(blocks2, blocks), d_var=var_error(var2, var), piv_min=float(piv.min()),
+               piv_max=float(piv.max()))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def reference_hp(name):
+    """50 digits (mpmath): -> dict(pd (False: H is not positive definite at 50 digits, nothing else is returned), blocks, var (rounded to
+    doubles, read like reference's), piv_min, piv_max, rcond (their ratio: the pivots of the Cholesky factor of the Jacobi-scaled reduced
+    system), err_blocks, err_var (reference's np.linalg.inv against these, max), err2_blocks, err2_var (the second evaluation's; inf
+    where it failed), rcond_np, rcond_np_err (numpy's pivot ratio and its relative error))"""
+    import mpmath as mp
+    pd = problem(name)
+    F = len(pd.frame_state)
+    H, idx, lo, fr, lm = linearized(name)
+    assert H.shape[0] <= 135, "reference_hp is for the small cases"
+    order = np.concatenate([lm, fr]).astype(int)
+    n, nl = len(order), len(lm)
+    with mp.workdps(50):
+        A = [[mp.mpf(float(H[order[i], order[j]])) for j in range(i + 1)] for i in range(n)]
+        Lm = []
+        for i in range(n):   # L L^T = H, row by row
+            row = []
+            for j in range(i):
+                row.append((A[i][j] - mp.fdot(row[:j], Lm[j][:j])) / Lm[j][j])
+            piv = A[i][i] - mp.fdot(row, row)
+            if not piv > 0:
+                return dict(pd=False)
+            row.append(mp.sqrt(piv))
+            Lm.append(row)
+        Y = []   # L^-1 by columns: Y[c][i - c], i >= c
+        for c in range(n):
+            col = [1 / Lm[c][c]]
+            for i in range(c + 1, n):
+                col.append(-mp.fdot(Lm[i][c:i], col) / Lm[i][i])
+            Y.append(col)
+        pos = -np.ones(H.shape[0], int)
+        pos[order] = np.arange(n)
+
+        def sig(a, b):   # (H^-1)_ab = sum_k Y_ka Y_kb
+            a, b = pos[a], pos[b]
+            m = max(a, b)
+            return float(mp.fdot(Y[a][m - a:], Y[b][m - b:]))
+        blocks = np.zeros((F, 15, 15))
+        for f in range(F):
+            ii = idx[15 * f:15 * f + 15]
+            for r in range(15):
+                for c in range(r + 1):
+                    if ii[r] >= 0 and ii[c] >= 0:
+                        blocks[f, r, c] = blocks[f, c, r] = sig(ii[r], ii[c])
+        var = np.array([sig(l, l) if l >= 0 else 0.0 for l in lo])
+        # the trailing block of L is the factor of S; of D S D it is D L: pivot_i = L_ii^2 / S_ii, S_ii = sum_k L_ik^2 over that block
+        piv = [Lm[i][i] ** 2 / mp.fdot(Lm[i][nl:], Lm[i][nl:]) for i in range(nl, n)]
+        piv_min, piv_max = min(piv), max(piv)
+        rcond = float(piv_min / piv_max)
+        piv_min, piv_max = float(piv_min), float(piv_max)
+    r = reference(name)
+    ok2 = r["blocks2"] is not None
+    emax = lambda e: float(e.max()) if len(e) else 0.0   # noqa: E731
+    rc_np = r["piv_min"] / r["piv_max"]
+    return dict(pd=True, blocks=blocks, var=var, piv_min=piv_min, piv_max=piv_max, rcond=rcond,
+                err_blocks=emax(block_error(r["blocks"], blocks)), err_var=emax(var_error(r["var"], var)),
+                err2_blocks=emax(block_error(r["blocks2"], blocks)) if ok2 else np.inf, err2_var=emax(var_error(r["var2"], var)) if ok2 else np.inf,
+                rcond_np=rc_np, rcond_np_err=abs(rc_np - rcond) / rcond)
 
 
 def block_error(got, ref):
@@ -106,11 +258,53 @@ def tolerance(name):
     return max(1e-9, 50 * d_b), max(1e-9, 50 * d_v)
 
 
-def table():
-    rows = ["| case | na | free landmarks | cond (scaled S) | d_ref blocks | d_ref variances | tol blocks | tol variances |", "|---|---|---|---|---|---|---|---|"]
-    for name in CASES:
+def tolerance_hp(name):
+    """-> (blocks, variances) of an ill-conditioned member, against reference_hp: 50 times the second evaluation's own error against
+    the same reference (the largest over the blocks / the variances), plus 1e-12"""
+    h = reference_hp(name)
+    return 50 * h["err2_blocks"] + 1e-12, 50 * h["err2_var"] + 1e-12
+
+
+def rcond_tolerance(name):
+    """-> relative tolerance of the device's rcond: against reference_hp's pivot ratio 50 times numpy's own relative error plus 1e-12
+    (HP_CASES); against numpy's pivot ratio 1e-6 (the large cases: cond <= 4e5, a pivot moves by about cond n eps = 1e-7)"""
+    return 50 * reference_hp(name)["rcond_np_err"] + 1e-12 if name in HP_CASES else 1e-6
+
+
+def factorable(name):
+    """numpy's Cholesky of the scaled S succeeds with min pivot > 100 na 2^-52 max pivot: the device (threshold na 2^-52) must answer"""
+    r = reference(name)
+    return r["blocks2"] is not None and r["piv_min"] > 100 * r["na"] * 2.0 ** -52 * r["piv_max"]
+
+
+def table(names=None, measured=None):
+    """The cases as a markdown table.  measured: {case: dict(status, err_blocks, err_var, rcond)} of a GPU run (tools/covariance.py)
+    adds its columns -- the errors against the 50-digit reference where the case has one, else against np.linalg.inv.  The tolerance of
+    an ill-conditioned member is tolerance_hp, of every other case max(1e-9, 50 d_ref)."""
+    head = ["case", "na", "n16", "free landmarks", "cond (scaled S)", "d_ref blocks", "d_ref variances", "tol blocks", "tol variances",
+            "inv vs 50 digits", "Schur route vs 50 digits", "rcond 50 digits", "numpy rcond rel. error"]
+    if measured is not None:
+        head += ["GPU status", "GPU blocks", "GPU variances", "GPU rcond rel. error", "rcond tolerance"]
+    rows = ["| " + " | ".join(head) + " |", "|" + "---|" * len(head)]
+    for name in names or TABLE_CASES:
         r = reference(name)
-        tb, tv = tolerance(name)
-        rows.append("| %s | %d | %d | %.2e | %.2e | %.2e | %.2e | %.2e |" % (name, r["na"], r["nla"], r["cond"], r["d_blocks"].max(),
-                                                                       r["d_var"].max() if len(r["d_var"]) else 0.0, tb, tv))
+        hp = reference_hp(name) if name in HP_CASES else None
+        tb, tv = tolerance_hp(name) if name in ILL_CASES and hp["pd"] else tolerance(name)
+        if hp is None:
+            tail = " | | | |"
+        elif not hp["pd"]:
+            tail = " not positive definite | | | |"
+        else:
+            tail = " %.2e | %.2e | %.4e | %.2e |" % (max(hp["err_blocks"], hp["err_var"]), max(hp["err2_blocks"], hp["err2_var"]), hp["rcond"],
+                                                hp["rcond_np_err"])
+        if measured is not None:
+            m = measured[name]
+            if m["status"] == 0:
+                want = hp["rcond"] if hp is not None else r["piv_min"] / r["piv_max"]
+                tail += " 0 | %.2e | %.2e | %.2e | %.2e |" % (m["err_blocks"], m["err_var"], abs(m["rcond"] - want) / want, rcond_tolerance(name))
+            else:
+                tail += " %d | | | | |" % m["status"]
+        rows.append("| %s | %d | %d | %d | %.2e | %.2e | %.2e | %.2e | %.2e |%s" % (
+            name, r["na"], 16 * ((r["na"] + 15) // 16), r["nla"], r["cond"], r["d_blocks"].max(), r["d_var"].max() if len(r["d_var"]) else 0.0,
+            tb, tv, tail))
     return "\n".join(rows)
