@@ -1,7 +1,8 @@
 // Host-side access to the staging of a bundle-adjustment problem (xrslam_amd/csrc/ba_stage.hpp) for tests/test_ba_stage_host.py: the
 // problem goes in as plain arrays; the counted sizes, the gather tables, the pointer sets (as raw 8-byte slots of BaPtrs, with the
-// slot of every listed member) and the effect of the exchange come back as integers.  -DBA_STAGE_HOST_MAIN: a stand-alone program
-// that stages four small problems into exactly sized heap blocks, for a run under the sanitizers.
+// slot of every listed member), the effect of the exchange, the three scratch layouts and the marginalisation's view as a BA problem
+// come back as integers.  -DBA_STAGE_HOST_MAIN: a stand-alone program that stages four small problems and a marginalisation and lays
+// the scratch blocks out in exactly sized heap blocks, for a run under the sanitizers.
 #include "../../xrslam_amd/csrc/ba_stage.hpp"
 
 #include <cstddef>
@@ -130,6 +131,56 @@ void hc_stage_swap(unsigned long long *a_slots, unsigned long long *b_slots) {
     std::memcpy(b_slots, &b, sizeof(b));
 }
 
+// the scratch layouts, members in declaration order.  marg: 16 offsets, bytes, host_bytes; cov: 9 offsets, bytes; preint: 5, bytes
+void hc_marg_scratch(int N, int R, unsigned long long *out18) {
+    const MargScratch m = marg_scratch(N, R);
+    const size_t v[18] = {m.Hm, m.bm, m.T2, m.A, m.bp, m.B, m.V, m.si, m.iv, m.st, m.lam, m.sup, m.As, m.bs, m.Ss, m.ivs, m.bytes, m.host_bytes};
+    for (int i = 0; i < 18; ++i) out18[i] = v[i];
+}
+void hc_cov_scratch(int n16, int nt, int n_sel, int groups, int full, int L, unsigned long long *out10) {
+    const CovScratch s = cov_scratch(n16, nt, n_sel, groups, full != 0, L);
+    const size_t v[10] = {s.st, s.A, s.Li, s.ds, s.cols, s.B, s.Sig, s.out, s.var, s.bytes};
+    for (int i = 0; i < 10; ++i) out10[i] = v[i];
+}
+void hc_preint_scratch(int n_jobs, int total_samples, unsigned long long *out6) {
+    const PreintScratch s = preint_scratch(n_jobs, total_samples);
+    const size_t v[6] = {s.jobs, s.smp, s.noise, s.out, s.st, s.bytes};
+    for (int i = 0; i < 6; ++i) out6[i] = v[i];
+}
+// sizeof(CovStatus), sizeof(PreintJob)
+void hc_scratch_sizes(long long *out2) {
+    out2[0] = sizeof(CovStatus);
+    out2[1] = sizeof(PreintJob);
+}
+
+// marg_problem_view of *M.  ints9: n_frames n_landmarks n_obs n_rot n_imu prior_n max_iterations, 1 if landmark_fix is the lfix copy,
+// 1 if frame_state / frame_fix / inv_depth are the other three copies; ptrs (32): every other pointer member followed by what it must
+// equal (M's array, or null for the rotation factors); ext16: cam_q_bc cam_p_bc imu_q_bi imu_p_bi sqrt_inv_cov;
+// state / fix / depth / lfix: the content of the copies (16 K, K, L, max(L, 1) entries)
+void hc_marg_view(const xrhip_marg_problem *M, int *ints9, unsigned long long *ptrs, double *ext16, double *state, unsigned char *fix,
+                  double *depth, unsigned char *lfix) {
+    std::vector<double> vs, vd;
+    std::vector<uint8_t> vf, vl;
+    const xrhip_ba_problem P = marg_problem_view(*M, vs, vf, vd, vl);
+    const int iv[9] = {P.n_frames, P.n_landmarks, P.n_obs, P.n_rot, P.n_imu, P.prior_n, P.max_iterations,
+                       P.landmark_fix == vl.data(), P.inv_depth == vd.data() && P.frame_state == vs.data() && P.frame_fix == vf.data()};
+    std::memcpy(ints9, iv, sizeof(iv));
+    const void *pp[] = {P.obs_tgt, M->obs_tgt, P.obs_ref, M->obs_ref, P.obs_lm, M->obs_lm, P.obs_z_tgt, M->obs_z_tgt, P.obs_z_ref, M->obs_z_ref,
+                        P.imu_i, M->imu_i, P.imu_j, M->imu_j, P.imu_data, M->imu_data, P.prior_frames, M->prior_frames,
+                        P.prior_sqrt_info, M->prior_sqrt_info, P.prior_infovec, M->prior_infovec, P.prior_lin, M->prior_lin,
+                        P.rot_tgt, nullptr, P.rot_ref, nullptr, P.rot_z_tgt, nullptr, P.rot_z_ref, nullptr};
+    for (size_t i = 0; i < sizeof(pp) / sizeof(pp[0]); ++i) ptrs[i] = (unsigned long long)reinterpret_cast<uintptr_t>(pp[i]);
+    std::memcpy(ext16, P.cam_q_bc, sizeof(double) * 4);
+    std::memcpy(ext16 + 4, P.cam_p_bc, sizeof(double) * 3);
+    std::memcpy(ext16 + 7, P.imu_q_bi, sizeof(double) * 4);
+    std::memcpy(ext16 + 11, P.imu_p_bi, sizeof(double) * 3);
+    std::memcpy(ext16 + 14, P.sqrt_inv_cov, sizeof(P.sqrt_inv_cov));
+    std::memcpy(state, vs.data(), sizeof(double) * vs.size());
+    std::memcpy(fix, vf.data(), vf.size());
+    if (!vd.empty()) std::memcpy(depth, vd.data(), sizeof(double) * vd.size());
+    std::memcpy(lfix, vl.data(), vl.size());
+}
+
 }   // extern "C"
 
 #ifdef BA_STAGE_HOST_MAIN
@@ -195,6 +246,72 @@ static int stage_one(int F, int L, int M, int MR, int NI, int NP) {
     return staged_ctl->iteration;   // 0: the control block went where BaPtrs::ctl says it is
 }
 
+// the scratch layouts in blocks of exactly the sizes they report: the first byte of every buffer and the last of the last one
+static void touch(std::vector<char> &blk, std::initializer_list<size_t> offs, size_t last_byte) {
+    for (size_t o : offs) blk[o] = 1;
+    blk[last_byte] = 1;
+}
+static void scratch_all() {
+    const int ms[3][2] = {{30, 15}, {165, 150}, {527, 512}};
+    for (const auto &s : ms) {
+        const MargScratch m = marg_scratch(s[0], s[1]);
+        std::vector<char> blk(m.bytes);
+        touch(blk, {m.Hm, m.bm, m.T2, m.A, m.bp, m.B, m.V, m.si, m.iv, m.st, m.lam, m.sup, m.As, m.bs, m.Ss, m.ivs}, m.ivs + D8 * s[1] - 1);
+    }
+    const int cs[4][6] = {{16, 1, 1, 1, 0, 0}, {176, 11, 11, 11, 1, 100}, {960, 60, 64, 64, 1, 100}, {960, 60, 65, 64, 0, 0}};
+    for (const auto &s : cs) {
+        const CovScratch c = cov_scratch(s[0], s[1], s[2], s[3], s[4] != 0, s[5]);
+        std::vector<char> blk(c.bytes);
+        touch(blk, {c.st, c.A, c.Li, c.ds, c.cols, c.B, c.Sig, c.out, c.var}, c.var + D8 * std::max(s[5], 1) - 1);
+    }
+    const int ps[2][2] = {{1, 1}, {12, 240}};
+    for (const auto &s : ps) {
+        const PreintScratch p = preint_scratch(s[0], s[1]);
+        std::vector<char> blk(p.bytes);
+        touch(blk, {p.jobs, p.smp, p.noise, p.out, p.st}, p.st + 2 * sizeof(int) * s[0] - 1);
+    }
+}
+
+// a marginalisation (three frames, a prior on two, both IMU factors of the victim, three observations) staged through its view
+static int marg_view_one() {
+    const int K = 3, L = 2, M = 3, NI = 2, NP = 2;
+    std::vector<double> state((size_t)16 * K, 0.25), depth(L, 0.5), z((size_t)3 * M, 1.0), imu_data((size_t)XRHIP_IMU_DIM * NI, 0.0);
+    std::vector<double> pS((size_t)225 * NP * NP, 0.0), pinfo((size_t)15 * NP, 0.0), plin((size_t)16 * NP, 0.0);
+    const int tgt[M] = {1, 1, 2}, ref[M] = {0, 0, 1}, lm[M] = {0, 1, 1}, ii[NI] = {0, 1}, ij[NI] = {1, 2}, pf[NP] = {0, 2};
+    xrhip_marg_problem Mp;
+    std::memset(&Mp, 0, sizeof(Mp));
+    Mp.n_frames = K;
+    Mp.victim = 1;
+    Mp.frame_state = state.data();
+    Mp.prior_n = NP;
+    Mp.prior_frames = pf;
+    Mp.prior_sqrt_info = pS.data();
+    Mp.prior_infovec = pinfo.data();
+    Mp.prior_lin = plin.data();
+    Mp.n_imu = NI;
+    Mp.imu_i = ii;
+    Mp.imu_j = ij;
+    Mp.imu_data = imu_data.data();
+    Mp.n_landmarks = L;
+    Mp.inv_depth = depth.data();
+    Mp.n_obs = M;
+    Mp.obs_tgt = tgt;
+    Mp.obs_ref = ref;
+    Mp.obs_lm = lm;
+    Mp.obs_z_tgt = Mp.obs_z_ref = z.data();
+    std::vector<double> vs, vd;
+    std::vector<uint8_t> vf, vl;
+    const xrhip_ba_problem P = marg_problem_view(Mp, vs, vf, vd, vl);
+    BaDims d;
+    StageIndex ix;
+    if (stage_index(&P, 0, d, ix)) return 1;
+    BaCtl ctl;
+    std::memset(&ctl, 0, sizeof(ctl));
+    std::vector<char> in_host(stage_layout(d).in_bytes);
+    stage_copy_inputs(in_host.data(), d, &P, ix, ctl);
+    return d.na == 15 * K && d.nla == L && P.max_iterations == 0 ? 0 : 1;
+}
+
 int main() {
     const int shapes[4][6] = {{1, 0, 0, 0, 0, 0}, {2, 1, 1, 0, 0, 0}, {3, 17, 40, 3, 2, 2}, {13, 100, 700, 0, 12, 1}};
     for (const auto &s : shapes)
@@ -202,6 +319,11 @@ int main() {
             std::printf("ba_stage_host: shape F=%d L=%d M=%d failed\n", s[0], s[1], s[2]);
             return 1;
         }
+    scratch_all();
+    if (marg_view_one()) {
+        std::printf("ba_stage_host: marginalisation view failed\n");
+        return 1;
+    }
     std::printf("ba_stage_host OK\n");
     return 0;
 }

@@ -10,7 +10,7 @@ are measured in those scalings, REF being the reference (the oracle):
     deta    = max over the support of |eta_i - REF_i| / (sqrt(REF_ii) |iv_REF|)
 
 The support is where(diag(REF) > 0).  It must be the same set for both, and outside it the rows and columns of Lambda and the
-entries of eta must be exactly zero (what km_support / km_expand promise, and what the oracle's Jacobi eigen-solver leaves).
+entries of eta must be exactly zero (what km_support and the expansions of km_chol / km_jacobi promise, and what the oracle's Jacobi eigen-solver leaves).
 
 Tolerances.  TOL[family] = 100 x the largest deviation of the ORACLE from an independent Schur complement carried out in np.longdouble
 (tests/test_oracle_ba.py::_numpy_marginal) over the family's cases; measured on the CPU by

@@ -4,7 +4,10 @@ tables, the device layout of both arenas, the second pointer set of a speculativ
 Device addresses feed cache and channel behaviour, so the layout is frozen: LAYOUT below is the put / carve sequence of stage_problem
 as it stood before the layout moved into one table, transcribed once -- order, arena and size formula of every buffer -- and SPEC_SET
 the members that the solve re-based into the second workspace and exchanged when a speculation was taken.  Every expected value here
-comes from these literals and from arithmetic in this file, not from a second call of the code under test."""
+comes from these literals and from arithmetic in this file, not from a second call of the code under test.
+
+The same holds for the three scratch layouts that are not a staged problem's -- the marginalisation's, the covariance's and the
+pre-integration staging block's (MARG_SCRATCH, COV_SCRATCH, PREINT_SCRATCH below) -- and marg_problem_view is checked field by field."""
 import ctypes as C
 import os
 import re
@@ -114,7 +117,8 @@ SHAPES = {"frame_only": (1, 0, 0, 0, 0, 0), "one_obs": (2, 1, 1, 0, 0, 0), "odd"
 def hc():
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("ba_stage.hpp", "ba_plan.hpp", "ba_chain.hip.h", "ba_kernels.hip.h", "dense_lds.hip.h")]
+    deps = [SRC] + [os.path.join(CSRC, f) for f in ("ba_stage.hpp", "ba_plan.hpp", "ba_chain.hip.h", "ba_kernels.hip.h", "dense_lds.hip.h", "cov_kernels.hip.h",
+                                                       "marg_kernels.hip.h")]
     if not os.path.exists(OUT) or os.path.getmtime(OUT) < max(os.path.getmtime(f) for f in deps):
         os.makedirs(os.path.dirname(OUT), exist_ok=True)
         subprocess.check_call([HIPCC, "-x", "hip", "--offload-arch=gfx950", "-O1", "-std=c++17", "-fPIC", "-shared", SRC, "-o", OUT])
@@ -320,8 +324,141 @@ def test_empty_problem_tables_keep_one_entry(hc):
     assert table(hc, "imuf") == [-1, -1] and table(hc, "priorf") == [-1] and list(table(hc, "bias_ref")) == [0.0] * 6
 
 
+# ---------------------------------------------------------------------------------------------- the three scratch layouts
+# The bump256 sequences of marg_launch, xrhip_ba_covariance and preint_stage as they stood in ba_api.hip before the layouts moved
+# into ba_stage.hpp, transcribed once: (name, bytes), in order.  COV_STATUS / PREINT_JOB = sizeof(CovStatus) / sizeof(PreintJob).
+COV_STATUS, PREINT_JOB = 24, 72
+MARG_SCRATCH = [
+    ("Hm", lambda N, R: 8 * N * N), ("bm", lambda N, R: 8 * N), ("T2", lambda N, R: 8 * R * 15),
+    ("A", lambda N, R: 8 * R * R), ("bp", lambda N, R: 8 * R), ("B", lambda N, R: 8 * R * R),
+    ("V", lambda N, R: 8 * R * R), ("si", lambda N, R: 8 * R * R), ("iv", lambda N, R: 8 * R),
+    ("st", lambda N, R: 4 * 8), ("lam", lambda N, R: 8 * 2), ("sup", lambda N, R: 4 * R),
+    ("As", lambda N, R: 8 * R * R), ("bs", lambda N, R: 8 * R), ("Ss", lambda N, R: 8 * R * R), ("ivs", lambda N, R: 8 * R),
+]
+COV_SCRATCH = [
+    ("st", lambda n16, nt, n_sel, groups, full, L: COV_STATUS),
+    ("A", lambda n16, nt, n_sel, groups, full, L: 8 * n16 * n16),
+    ("Li", lambda n16, nt, n_sel, groups, full, L: 8 * 256 * nt),
+    ("ds", lambda n16, nt, n_sel, groups, full, L: 8 * n16),
+    ("cols", lambda n16, nt, n_sel, groups, full, L: 4 * 16 * (n_sel + nt)),
+    ("B", lambda n16, nt, n_sel, groups, full, L: 8 * 16 * n16 * max(groups, 1)),
+    ("Sig", lambda n16, nt, n_sel, groups, full, L: 8 * n16 * n16 if full else 8),
+    ("out", lambda n16, nt, n_sel, groups, full, L: 8 * 225 * max(n_sel, 1)),
+    ("var", lambda n16, nt, n_sel, groups, full, L: 8 * max(L, 1)),
+]
+PREINT_SCRATCH = [
+    ("jobs", lambda n_jobs, total: PREINT_JOB * n_jobs), ("smp", lambda n_jobs, total: 8 * 7 * total),
+    ("noise", lambda n_jobs, total: 8 * 36),
+    ("out", lambda n_jobs, total: 8 * IMU_DIM * n_jobs + 2 * 4 * n_jobs),   # the results, then the status and early-delta words
+]
+SEL_BATCH = 64   # selected frames per launch of kc_selected_inverse
+
+
+def scratch_expected(table, *args):
+    """-> ([offset of every entry], bytes the block must hold) from a table above alone"""
+    used, offs = 0, []
+    for _, size in table:
+        off, used = bump(used, size(*args))
+        offs.append(off)
+    return offs, used + 256
+
+
+def cov_args(na, n_sel, want_var, L, nla=1):
+    """the arguments xrhip_ba_covariance lays its scratch out with, as it derived them before the layout moved"""
+    full = bool(want_var and L > 0 and nla > 0)
+    n16 = (na + 15) // 16 * 16
+    nt = n16 // 16
+    return n16, nt, n_sel, max(nt if full else 0, min(n_sel, SEL_BATCH)), full, L
+
+
+def _scratch(hc, fn, n, *args):
+    out = np.zeros(n, np.uint64)
+    getattr(hc, fn)(*args, _ptr(out))
+    return [int(v) for v in out]
+
+
+def test_scratch_struct_sizes(hc):
+    sizes = np.zeros(2, np.int64)
+    hc.hc_scratch_sizes(_ptr(sizes))
+    assert (int(sizes[0]), int(sizes[1])) == (COV_STATUS, PREINT_JOB)
+
+
+@pytest.mark.parametrize("N,R", [(30, 15), (165, 150), (527, 512)])   # two frames; the pipeline's full window; the largest accepted
+def test_marg_scratch_is_the_frozen_one(hc, N, R):
+    offs, total = scratch_expected(MARG_SCRATCH, N, R)
+    got = _scratch(hc, "hc_marg_scratch", 18, N, R)
+    assert got[:16] == offs and got[16] == total
+    assert got[17] == 8 * (R * R + R) + 64 + 4 * 8     # the pinned readback: sqrt_info, infovec, status words
+    assert all(o % 256 == 0 for o in offs) and offs == sorted(set(offs)) and offs[0] == 0
+    if (N, R) == (30, 15):
+        assert total <= 1 << 20      # stays under the workspace's 1 MiB floor
+    if (N, R) == (165, 150):
+        assert total > 1 << 20       # ... and this one does not (tests/test_marg_shapes_gpu.py relies on both)
+
+
+# na, selected frames, variances asked, landmarks: one free frame; a full window; the cap on both sides of SEL_BATCH
+@pytest.mark.parametrize("L", (0, 100))
+@pytest.mark.parametrize("na,n_sel,want_var", [(15, 1, False), (165, 11, True), (960, 64, True), (960, 65, True)])
+def test_cov_scratch_is_the_frozen_one(hc, na, n_sel, want_var, L):
+    args = cov_args(na, n_sel, want_var, L)
+    n16, nt, _, groups, full, _ = args
+    assert full == (want_var and L > 0)
+    if na == 960:                  # 64 | 65 selected: the right-hand-side groups stop at SEL_BATCH, the column lists and blocks go on
+        assert (n16, nt, groups) == (960, 60, 64)
+    offs, total = scratch_expected(COV_SCRATCH, *args)
+    got = _scratch(hc, "hc_cov_scratch", 10, n16, nt, n_sel, groups, int(full), L)
+    assert got[:9] == offs and got[9] == total
+    assert all(o % 256 == 0 for o in offs) and offs == sorted(set(offs)) and offs[0] == 0
+    names = [n for n, _ in COV_SCRATCH]
+    if not full:                                       # the 8-byte stand-in of the inverse takes one 256-byte slot
+        assert offs[names.index("out")] - offs[names.index("Sig")] == 256
+
+
+@pytest.mark.parametrize("n_jobs,total", [(1, 1), (12, 240)])
+def test_preint_scratch_is_the_frozen_one(hc, n_jobs, total):
+    offs, bytes_ = scratch_expected(PREINT_SCRATCH, n_jobs, total)
+    got = _scratch(hc, "hc_preint_scratch", 6, n_jobs, total)
+    assert got[:4] == offs and got[5] == bytes_
+    assert got[4] == offs[3] + 8 * IMU_DIM * n_jobs     # the status words follow the results directly, inside the same bump
+
+
+def test_marg_problem_view(hc):
+    """Three frames, victim 1, a prior on frames 0 and 2, both IMU factors of the victim, three observations of two landmarks: every
+    field of the BA problem the marginalisation is staged as.  Counts and the factor arrays are the marginalisation's own; frames and
+    landmarks are copies with every block free; no rotation factor; no iteration."""
+    from xrslam_amd import abi
+    rng = np.random.default_rng(5)
+    K, L, NP = 3, 2, 2
+    md = abi.MargProblemData(
+        rng.normal(size=(K, 16)), 1, rng.normal(size=7), rng.normal(size=7), [460.0, 457.0],
+        dict(frames=[0, 2], sqrt_info=rng.normal(size=(15 * NP, 15 * NP)), infovec=rng.normal(size=15 * NP), lin=rng.normal(size=(NP, 16))),
+        dict(i=[0, 1], j=[1, 2], data=rng.normal(size=(2, IMU_DIM))), [0.5, 0.25],
+        dict(tgt=[1, 1, 2], ref=[0, 0, 1], lm=[0, 1, 1], z_tgt=rng.normal(size=(3, 3)), z_ref=rng.normal(size=(3, 3))))
+    M = md.struct()
+    ints, ptrs, ext = np.zeros(9, np.int32), np.zeros(32, np.uint64), np.zeros(16)
+    state, fix, depth, lfix = np.full((K, 16), np.nan), np.full(K, 9, np.uint8), np.full(L, np.nan), np.full(L, 9, np.uint8)
+    hc.hc_marg_view(C.byref(M), _ptr(ints), _ptr(ptrs), _ptr(ext), _ptr(state), _ptr(fix), _ptr(depth), _ptr(lfix))
+    # n_frames n_landmarks n_obs n_rot n_imu prior_n max_iterations | landmark_fix, then frame_state / frame_fix / inv_depth are the copies
+    assert list(ints) == [K, L, 3, 0, 2, NP, 0, 1, 1]
+    mine = [md.obs_tgt, md.obs_ref, md.obs_lm, md.obs_z_tgt, md.obs_z_ref, md.imu_i, md.imu_j, md.imu_data, md.prior_frames,
+            md.prior_sqrt_info, md.prior_infovec, md.prior_lin]
+    got, want = [int(v) for v in ptrs[0::2]], [a.ctypes.data for a in mine] + [0] * 4      # the rotation factors' arrays: null
+    assert got == want and [int(v) for v in ptrs[1::2]] == want
+    np.testing.assert_array_equal(ext, np.concatenate([md.cam_ext[:4], md.cam_ext[4:7], md.imu_ext[:4], md.imu_ext[4:7], md.sqrt_inv_cov[:2]]))
+    np.testing.assert_array_equal(state, md.frame_state)
+    np.testing.assert_array_equal(depth, md.inv_depth)
+    assert not fix.any() and not lfix.any()
+    # no landmarks: the depth copy is empty, the constant flags keep one entry
+    md0 = abi.MargProblemData(md.frame_state, 0, md.cam_ext, md.imu_ext, md.sqrt_inv_cov, None, None, np.zeros(0), None)
+    M0 = md0.struct()
+    lfix[:] = 9
+    hc.hc_marg_view(C.byref(M0), _ptr(ints), _ptr(ptrs), _ptr(ext), _ptr(state), _ptr(fix), _ptr(depth), _ptr(lfix))
+    assert list(ints) == [K, 0, 0, 0, 0, 0, 0, 1, 1] and list(lfix) == [0, 9]
+
+
 def test_staging_under_sanitizers(tmp_path):
-    """the same source as a stand-alone program: the four shapes staged into blocks of exactly the sizes the layout reports"""
+    """the same source as a stand-alone program: the four shapes staged into blocks of exactly the sizes the layout reports, the three
+    scratch layouts touched at both ends of such blocks, and a marginalisation staged through marg_problem_view"""
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
     exe = str(tmp_path / "ba_stage_host")

@@ -79,6 +79,28 @@ def test_selection(ctx, name):
     assert np.array_equal(ctx.covariance(pd, many)["blocks"], every[many])
 
 
+def test_scratch_that_moves_between_requests():
+    """One context of its own: k6 (na = 90: 0.17 MiB of scratch, the 1 MiB floor), k21 (na = 315: 1.7 MiB, so the block is reallocated
+    behind a drained stream and every buffer moves), k6 again in the larger block -- every frame's block within the case's tolerance."""
+    from tests.test_ba_stage_host import COV_SCRATCH, cov_args, scratch_expected
+    from xrslam_amd import ba
+    need = {name: scratch_expected(COV_SCRATCH, *cov_args(15 * K, K, False, len(cm.problem(name).inv_depth)))[1]
+            for name, K in (("k6", 6), ("k21", 21))}
+    assert need["k6"] <= 1 << 20 < need["k21"]
+    c = ba.BaContext()
+    try:
+        for name in ("k6", "k21", "k6"):
+            pd = cm.problem(name).copy()
+            F = len(pd.frame_state)
+            assert cm.reference(name)["na"] == 15 * F
+            out = c.covariance(pd, np.arange(F))
+            assert out["status"] == 0
+            _check_blocks(name, out["blocks"], np.arange(F))
+            _check_zeros(pd, out["blocks"])
+    finally:
+        c.close()
+
+
 def test_schur_study_mode_does_not_reach_the_covariance(ctx):
     """A context left in the bf16 study mode of the Schur contraction (xrhip_ba_debug_set_schur_precision) still computes the
     covariance's Schur product in f64: the same bits as before."""

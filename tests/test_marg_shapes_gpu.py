@@ -124,6 +124,27 @@ def test_both_paths_are_reached_with_a_victim_that_is_not_frame_0(ctx, bo):
     assert PATHS["chained_k11_v2"][4] == 1 and PATHS["chained_k11_vlast"][4] == 1
 
 
+def test_workspace_that_moves_between_marginalisations(bo):
+    """One context of its own: K = 2 (N = 30, R = 15: the scratch stays under the workspace's 1 MiB floor), K = 11 (N = 165, R = 150:
+    about 1.3 MiB, so the workspace is reallocated and every buffer moves), K = 2 again in the larger block.  Each is a first window's
+    frame-0 marginalisation (make_window(K, L, seed), moved off the prior's linearisation point), held to the oracle in the "first"
+    family's tolerance like the cases above, and took the path its marginal matrix demands."""
+    from tests.test_ba_stage_host import MARG_SCRATCH, scratch_expected
+    from tests.test_oracle_ba import _numpy_marginal
+    from xrslam_amd import ba
+    assert scratch_expected(MARG_SCRATCH, 30, 15)[1] <= 1 << 20 < scratch_expected(MARG_SCRATCH, 165, 150)[1]
+    small, large = mc.marg_problem(mc.first_window(2, 80, 22), 0), mc.marg_problem(mc.first_window(11, 150, 21), 0)
+    c = ba.BaContext()
+    try:
+        for tag, md in (("k2", small), ("k11", large), ("k2_again", small)):
+            assert 15 * (len(md.frame_state) - 1) == {"k2": 15, "k11": 150, "k2_again": 15}[tag]
+            st, _, _ = _parity(c, bo, md, "first", "moving_" + tag)
+            want = mm.predicted_path(_numpy_marginal(md)[0])
+            assert want is not None and st[4] == want, (tag, st)
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("victim,n", [(2, 0), (5, 0), (2, 1), (4, 1)])
 def test_window_left_by_a_marginalisation_off_frame_0_solves_as_the_oracles(ctx, bo, victim, n):
     """the generalised next window (tests/marg_cases.py::next_window: the victim gone with its observations and the IMU factors that

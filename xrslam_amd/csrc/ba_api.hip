@@ -26,15 +26,33 @@ using namespace xrhip;
 
 namespace {
 
-struct Arena {   // bump allocator over one device buffer mirrored by a pinned host buffer
-    char *dev = nullptr, *host = nullptr;
-    size_t cap = 0, used = 0;
-    size_t take(size_t bytes) {
-        size_t off = (used + 255) & ~size_t(255);
-        used = off + bytes;
-        return off;
+// Grow-only buffers of a context.  reserve() keeps a block that holds `need` bytes; one that does not is freed and replaced by
+// max(need * headroom, floor) bytes -- nothing is carried over, and the address changes.  WHEN that happens is behaviour (device
+// addresses feed cache and channel behaviour), so every call site names its rule.
+struct Grow {
+    size_t headroom, floor;
+};
+constexpr Grow GROW_DOUBLE_1M{2, size_t(1) << 20}, GROW_DOUBLE{2, 0}, GROW_EXACT{1, 0};
+template <class T, bool PINNED> struct Buf {
+    T *p = nullptr;
+    size_t cap = 0;   // bytes
+    int reserve(size_t need, Grow g) {
+        if (need <= cap) return XRHIP_OK;
+        release();
+        const size_t bytes = std::max(need * g.headroom, g.floor);
+        if (PINNED) XR_HIP(hipHostMalloc((void **)&p, bytes, hipHostMallocDefault));
+        else XR_HIP(hipMalloc((void **)&p, bytes));
+        cap = bytes;
+        return XRHIP_OK;
+    }
+    void release() {
+        if (p) PINNED ? hipHostFree(p) : hipFree(p);
+        p = nullptr;
+        cap = 0;
     }
 };
+template <class T = char> using DevBuf = Buf<T, false>;
+template <class T = char> using PinnedBuf = Buf<T, true>;
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -90,13 +108,13 @@ struct xrhip_ba {
         bool handed_over = false;
         std::chrono::steady_clock::time_point t_hand;
     } begun;
-    Arena in;         // inputs (uploaded every solve)
-    char *work = nullptr;   // device-only workspace
-    size_t work_cap = 0;
-    char *work2 = nullptr;  // marginalisation / pre-integration workspace
-    size_t work2_cap = 0;
-    char *h_stage = nullptr;   // pinned staging for work2 transfers
-    size_t h_stage_cap = 0;
+    struct {          // inputs (uploaded every solve): the device arena and its pinned host mirror, grown together
+        DevBuf<> dev;
+        PinnedBuf<> host;
+    } in;
+    DevBuf<> work;    // device-only workspace
+    DevBuf<> work2;   // marginalisation workspace
+    PinnedBuf<> h_stage;   // pinned staging: the marginalisation's readback, a pre-integration batch
     BaCtl *h_ctl = nullptr;   // pinned; doubles as the zero-copy mailbox of kb_solve_try
     int *h_seq = nullptr;     // pinned; sequence number published by kb_solve_try after h_ctl / h_out
     int seq = 0;
@@ -104,15 +122,13 @@ struct xrhip_ba {
         bool pending = false;
         int K = 0, victim = 0, R = 0;
         std::vector<double> lin;
-        int *dst = nullptr, *dsup = nullptr;
-        double *lam = nullptr;   // km_chol's eigenvalue bound of the last marginalisation (xrhip_ba_debug_marg_guard)
-        double *As = nullptr, *bs = nullptr, *B = nullptr, *V = nullptr, *Ss = nullptr, *ivs = nullptr, *dsi = nullptr, *div = nullptr;
+        int *dst = nullptr;      // the status words and km_chol's eigenvalue bound of the last marginalisation, on the device
+        double *lam = nullptr;   // (xrhip_ba_debug_marg_guard)
     } marg;
     int preint_pending = 0;            // jobs of the pre-integration batch in flight (begin/end), 0 = none
-    size_t preint_o_out = 0, preint_o_st = 0;
+    PreintScratch preint_o{};          // where that batch (or the deferred one) sits in h_stage
     // a batch staged by xrhip_ba_preintegrate_after_solve: launched by the next xrhip_ba_solve behind its last kernel
     int preint_deferred = 0, preint_def_jac = 0, preint_def_cov = 0;
-    size_t preint_o_jobs = 0, preint_o_smp = 0, preint_o_noise = 0;
     // optional HIP-event profiling of kb_solve_try
     bool profiling = false;
     struct Timed {
@@ -128,8 +144,7 @@ struct xrhip_ba {
     std::vector<TimedChain> pending_chain;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
     xrhip_ba_stats stats = {0, 0, 0.0, 0, 0.0, 0, 0, 0.0, 0.0, 0};
-    char *cov_dev = nullptr;   // scratch of xrhip_ba_covariance (allocated by its first call, grown on demand)
-    size_t cov_cap = 0;
+    DevBuf<> cov_dev;   // scratch of xrhip_ba_covariance (allocated by its first call, grown on demand)
     hipEvent_t cov_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     double cov_ms[4] = {0.0, 0.0, 0.0, 0.0};
     const TinyArgs *tiny_args = nullptr;   // device address of the staged argument block (kb_tiny)
@@ -137,8 +152,7 @@ struct xrhip_ba {
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_mid = nullptr, ev_spec = nullptr;
     hipEvent_t ev_marg = nullptr;   // behind a marginalisation's last copy: collecting waits for THIS work, not for the stream
-    char *work_spec = nullptr;
-    size_t work_spec_cap = 0;
+    DevBuf<> work_spec;
     bool spec_outstanding = false;         // stream2 may still be writing work_spec / reading the input arena
     long spec_launched = 0, spec_taken = 0;   // development counters (XRHIP_HOSTPROF prints them)
     const uint4 *stage_src = nullptr;      // the staged problem: pinned host block (device-visible address) -> device arena
@@ -146,37 +160,18 @@ struct xrhip_ba {
     size_t stage_n16 = 0;
     void (*overlap_fn)(void *) = nullptr;   // xrhip_ba_solve_overlapped: pending host work of the caller (run at the first wait)
     void *overlap_arg = nullptr;
-    double *h_out = nullptr;  // pinned readback (states + depths)
-    size_t h_out_cap = 0;
+    PinnedBuf<double> h_out;  // pinned readback (states + depths)
     int lds_limit = 150 * 1024;
     int schur_mode = 0;                // study only (xrhip_ba_debug_set_schur_precision): 1 = f32, 2 = bf16 Schur contraction
     SolvePlan plan;                    // what the last solve was launched from (xrhip_ba_debug_last_route)
 };
 
 static int ensure_arena(xrhip_ba *c, size_t in_bytes, size_t work_bytes, size_t out_doubles) {
-    if (in_bytes > c->in.cap) {
-        if (c->in.dev) hipFree(c->in.dev);
-        if (c->in.host) hipHostFree(c->in.host);
-        c->in.dev = c->in.host = nullptr;
-        size_t cap = std::max(in_bytes * 2, size_t(1) << 20);
-        XR_HIP(hipMalloc(&c->in.dev, cap));
-        XR_HIP(hipHostMalloc(&c->in.host, cap, hipHostMallocDefault));
-        c->in.cap = cap;
-    }
-    if (work_bytes > c->work_cap) {
-        if (c->work) hipFree(c->work);
-        c->work = nullptr;
-        size_t cap = std::max(work_bytes * 2, size_t(1) << 20);
-        XR_HIP(hipMalloc(&c->work, cap));
-        c->work_cap = cap;
-    }
-    if (out_doubles > c->h_out_cap) {
-        if (c->h_out) hipHostFree(c->h_out);
-        c->h_out = nullptr;
-        XR_HIP(hipHostMalloc(&c->h_out, sizeof(double) * out_doubles * 2, hipHostMallocDefault));
-        c->h_out_cap = out_doubles * 2;
-    }
-    return XRHIP_OK;
+    int rc = c->in.dev.reserve(in_bytes, GROW_DOUBLE_1M);
+    if (!rc) rc = c->in.host.reserve(in_bytes, GROW_DOUBLE_1M);
+    if (!rc) rc = c->work.reserve(work_bytes, GROW_DOUBLE_1M);
+    if (!rc) rc = c->h_out.reserve(sizeof(double) * out_doubles, GROW_DOUBLE);
+    return rc;
 }
 
 static int validate(const xrhip_ba_problem *P) {
@@ -383,10 +378,10 @@ static int stage_problem(xrhip_ba *c, const xrhip_ba_problem *P, Staged &st, boo
     ctl.max_iterations = P->max_iterations;
     ctl.termination = XRHIP_BA_NO_CONVERGENCE;
     ctl.accepted_slot = -1;
-    stage_copy_inputs(c->in.host, d, P, ix, ctl);
-    stage_fill_ptrs(st.p, d, c->in.dev, c->work);
+    stage_copy_inputs(c->in.host.p, d, P, ix, ctl);
+    stage_fill_ptrs(st.p, d, c->in.dev.p, c->work.p);
     XR_HIP(hipHostGetDevicePointer((void **)&st.p.host_ctl, c->h_ctl, 0));
-    XR_HIP(hipHostGetDevicePointer((void **)&st.p.host_out, c->h_out, 0));
+    XR_HIP(hipHostGetDevicePointer((void **)&st.p.host_out, c->h_out.p, 0));
     XR_HIP(hipHostGetDevicePointer((void **)&st.p.host_seq, c->h_seq, 0));
     st.cam.q = Q4{P->cam_q_bc[0], P->cam_q_bc[1], P->cam_q_bc[2], P->cam_q_bc[3]};
     st.cam.p = V3{P->cam_p_bc[0], P->cam_p_bc[1], P->cam_p_bc[2]};
@@ -397,12 +392,12 @@ static int stage_problem(xrhip_ba *c, const xrhip_ba_problem *P, Staged &st, boo
     st.pl = plan_solve(d, (size_t)c->lds_limit, ba_switches());
     d.sred_tiled = st.pl.sred_tiled;   // a reduced system that does not fit LDS is written (kb_schur_aux) and factored (kb_solve_try) in the tiled layout, in place
     // the argument block of the single-launch solve travels with the problem
-    *reinterpret_cast<TinyArgs *>(c->in.host + lay.o_args) = st;
-    c->tiny_args = reinterpret_cast<const TinyArgs *>(c->in.dev + lay.o_args);
+    *reinterpret_cast<TinyArgs *>(c->in.host.p + lay.o_args) = st;
+    c->tiny_args = reinterpret_cast<const TinyArgs *>(c->in.dev.p + lay.o_args);
     char *host_dev = nullptr;   // device-visible address of the pinned staging block
-    XR_HIP(hipHostGetDevicePointer((void **)&host_dev, c->in.host, 0));
+    XR_HIP(hipHostGetDevicePointer((void **)&host_dev, c->in.host.p, 0));
     c->stage_src = (const uint4 *)host_dev;
-    c->stage_dst = (uint4 *)c->in.dev;
+    c->stage_dst = (uint4 *)c->in.dev.p;
     c->stage_n16 = (lay.in_bytes + 15) / 16;
     return defer_copy ? XRHIP_OK : launch_stage_copy(c, c->stream);
 }
@@ -662,19 +657,19 @@ void xrhip_ba_destroy(xrhip_ba *c) {
     if (c->stream2) hipStreamSynchronize(c->stream2);
     if (std::getenv("XRHIP_HOSTPROF") && c->spec_launched)
         std::fprintf(stderr, "[hostprof] speculative linearisations: %ld launched, %ld taken\n", c->spec_launched, c->spec_taken);
-    hipFree(c->work_spec);
-    hipFree(c->cov_dev);
+    c->work_spec.release();
+    c->cov_dev.release();
     for (hipEvent_t e : c->cov_ev)
         if (e) hipEventDestroy(e);
     if (c->ev_mid) hipEventDestroy(c->ev_mid);
     if (c->ev_marg) hipEventDestroy(c->ev_marg);
     if (c->ev_spec) hipEventDestroy(c->ev_spec);
     if (c->stream2) hipStreamDestroy(c->stream2);
-    hipFree(c->in.dev);
-    hipHostFree(c->in.host);
-    hipFree(c->work);
-    hipFree(c->work2);
-    hipHostFree(c->h_stage);
+    c->in.dev.release();
+    c->in.host.release();
+    c->work.release();
+    c->work2.release();
+    c->h_stage.release();
     hipHostFree(c->h_ctl);
     hipHostFree(c->h_seq);
     ba_resolve_pending(c);
@@ -682,7 +677,7 @@ void xrhip_ba_destroy(xrhip_ba *c) {
         hipEventDestroy(e.first);
         hipEventDestroy(e.second);
     }
-    hipHostFree(c->h_out);
+    c->h_out.release();
     hipStreamDestroy(c->stream);
     delete c;
 }
@@ -708,7 +703,7 @@ int xrhip_ba_solve_overlapped(xrhip_ba *c, const xrhip_ba_problem *P, xrhip_ba_s
 }
 // a batch staged by xrhip_ba_preintegrate_after_solve names frames of the solve it rides behind: a bad index drops the batch
 static int preint_deferred_check(xrhip_ba *c, const xrhip_ba_problem *P) {
-    const PreintJob *jobs = (const PreintJob *)(c->h_stage + c->preint_o_jobs);
+    const PreintJob *jobs = (const PreintJob *)(c->h_stage.p + c->preint_o.jobs);
     for (int k = 0; k < c->preint_deferred; ++k)
         if (jobs[k].bias_frame < 0 || jobs[k].bias_frame >= P->n_frames) {
             c->preint_deferred = 0;
@@ -830,7 +825,7 @@ static int collect_chain(xrhip_ba *c, const xrhip_ba_problem *P, const Staged &s
         std::snprintf(msg, sizeof(msg), "%s: trust-region loop did not terminate", who);
         return xr_fail(XRHIP_ESTATE, msg);
     }
-    std::memcpy(P->frame_state, c->h_out, sizeof(double) * 16 * d.F);
+    std::memcpy(P->frame_state, c->h_out.p, sizeof(double) * 16 * d.F);
     const double bytes = chain_bytes(d, *c->h_ctl);
     if (sub.e0) {
         timed->pending_chain.push_back({sub.e0, sub.e1, bytes});
@@ -906,7 +901,7 @@ int xrhip_ba_solve_linked(xrhip_ba *c2, const xrhip_ba_problem *P2, xrhip_ba_sum
     auto sequential = [&]() {
         int r = wait_flag(c1->h_seq, A.sub.seq, A.sub.stream, A.sub.rq, "xrhip_ba_solve_linked");
         if (r) return r;
-        std::memcpy(P2->frame_state + 16 * (size_t)link_second, c1->h_out + 16 * (size_t)link_first, sizeof(double) * 16);
+        std::memcpy(P2->frame_state + 16 * (size_t)link_second, c1->h_out.p + 16 * (size_t)link_first, sizeof(double) * 16);
         return xrhip_ba_solve_overlapped(c2, P2, s2, host_work, arg);
     };
     if (c1->group != c2->group || c2->begun.active || !any_free_block(P2) || !inputs_finite(P2)) return sequential();   // (refused there)
@@ -970,15 +965,10 @@ struct RoundIssuer {
     bool first = true, relin = true;   // GROUP: the next round request is the solve's first; whether the last round linearised
 
     int begin_spec() {   // the second buffer set mirrors the workspace
-        const size_t need = c->work_cap + spec_extra_bytes(st.d);
-        if (c->work_spec_cap < need) {
-            if (c->work_spec) hipFree(c->work_spec);
-            c->work_spec = nullptr;
-            XR_HIP(hipMalloc(&c->work_spec, need));
-            c->work_spec_cap = need;
-        }
+        const int rc = c->work_spec.reserve(c->work.cap + spec_extra_bytes(st.d), GROW_EXACT);
+        if (rc) return rc;
         st2 = st;
-        st2.p = spec_set(st.p, st.d, c->work, c->work_spec, c->work_cap);
+        st2.p = spec_set(st.p, st.d, c->work.p, c->work_spec.p, c->work.cap);
         return XRHIP_OK;
     }
     int request(int kind, int seq, int mode) {
@@ -1172,8 +1162,8 @@ static int ba_solve_impl(xrhip_ba *c, const xrhip_ba_problem *P, xrhip_ba_summar
     }
     if (!done) return xr_fail(XRHIP_ESTATE, "xrhip_ba_solve: trust-region loop did not terminate");
     // the optimised states (in place, like the reference)
-    std::memcpy(P->frame_state, c->h_out, sizeof(double) * 16 * d.F);
-    if (d.L && d.nla) std::memcpy(P->inv_depth, c->h_out + 16 * d.F, sizeof(double) * d.L);   // no free landmark: nothing moved
+    std::memcpy(P->frame_state, c->h_out.p, sizeof(double) * 16 * d.F);
+    if (d.L && d.nla) std::memcpy(P->inv_depth, c->h_out.p + 16 * d.F, sizeof(double) * d.L);   // no free landmark: nothing moved
     rc = preint_launch_deferred(c, P, nullptr);
     if (rc) return rc;
     kprof_accumulate(*c->h_ctl, d.na);
@@ -1276,25 +1266,16 @@ int xrhip_ba_covariance(xrhip_ba *c, const xrhip_ba_problem *P, const xrhip_cov_
     const int n16 = round_up(na, 16), nt = n16 / 16, n_sel = req->n_sel;
     constexpr int SEL_BATCH = 64;   // selected frames per kc_selected_inverse launch (bounds the right-hand-side scratch: <= 7.9 MB)
     const int groups = std::max(full ? nt : 0, std::min(n_sel, SEL_BATCH));   // (nt <= 60)
-    // ---- scratch
-    size_t w = 0;
-    const size_t o_st = bump256(w, sizeof(CovStatus)), o_A = bump256(w, D8 * (size_t)n16 * n16), o_Li = bump256(w, D8 * 256 * (size_t)nt), o_ds = bump256(w, D8 * n16);
-    const size_t o_cols = bump256(w, sizeof(int) * 16 * (size_t)(n_sel + nt)), o_B = bump256(w, D8 * 16 * (size_t)n16 * std::max(groups, 1));
-    const size_t o_Sig = bump256(w, full ? D8 * (size_t)n16 * n16 : 8), o_out = bump256(w, D8 * 225 * (size_t)std::max(n_sel, 1)), o_var = bump256(w, D8 * std::max(d.L, 1));
-    if (w + 256 > c->cov_cap) {
-        XR_HIP(hipStreamSynchronize(c->stream));
-        if (c->cov_dev) hipFree(c->cov_dev);
-        c->cov_dev = nullptr;
-        c->cov_cap = 0;
-        const size_t cap = std::max((w + 256) * 2, size_t(1) << 20);
-        XR_HIP(hipMalloc(&c->cov_dev, cap));
-        c->cov_cap = cap;
-    }
-    char *S = c->cov_dev;
-    CovStatus *st = (CovStatus *)(S + o_st);
-    double *A = (double *)(S + o_A), *Li = (double *)(S + o_Li), *ds = (double *)(S + o_ds), *B = (double *)(S + o_B);
-    double *Sig = (double *)(S + o_Sig), *dout = (double *)(S + o_out), *dvar = (double *)(S + o_var);
-    int *dcols = (int *)(S + o_cols);
+    // ---- scratch (a block that has to move is freed only once the stream has left it)
+    const CovScratch o = cov_scratch(n16, nt, n_sel, groups, full, d.L);
+    if (o.bytes > c->cov_dev.cap) XR_HIP(hipStreamSynchronize(c->stream));
+    rc = c->cov_dev.reserve(o.bytes, GROW_DOUBLE_1M);
+    if (rc) return rc;
+    char *S = c->cov_dev.p;
+    CovStatus *st = (CovStatus *)(S + o.st);
+    double *A = (double *)(S + o.A), *Li = (double *)(S + o.Li), *ds = (double *)(S + o.ds), *B = (double *)(S + o.B);
+    double *Sig = (double *)(S + o.Sig), *dout = (double *)(S + o.out), *dvar = (double *)(S + o.var);
+    int *dcols = (int *)(S + o.cols);
     // column lists: one group of 16 per selected frame (its 15 dofs), then -- full inverse -- one per tile column
     std::vector<int> cols(16 * (size_t)(n_sel + nt), -1);
     for (int k = 0; k < n_sel; ++k)
@@ -1420,34 +1401,17 @@ int xrhip_ba_debug_schur(xrhip_ba *c, const double *W, const double *w, int L, i
     return XRHIP_OK;
 }
 
-}   // extern "C"
-
-static int ensure_work2(xrhip_ba *c, size_t dev_bytes, size_t host_bytes) {
-    if (dev_bytes > c->work2_cap) {
-        if (c->work2) hipFree(c->work2);
-        c->work2 = nullptr;
-        size_t cap = std::max(dev_bytes * 2, size_t(1) << 20);
-        XR_HIP(hipMalloc(&c->work2, cap));
-        c->work2_cap = cap;
-    }
-    if (host_bytes > c->h_stage_cap) {
-        if (c->h_stage) hipHostFree(c->h_stage);
-        c->h_stage = nullptr;
-        size_t cap = std::max(host_bytes * 2, size_t(1) << 20);
-        XR_HIP(hipHostMalloc(&c->h_stage, cap, hipHostMallocDefault));
-        c->h_stage_cap = cap;
-    }
-    return XRHIP_OK;
-}
-
-extern "C" {
-
-// Marginalisation in two halves.  marg_launch stages the problem and queues EVERY kernel and copy of the Cholesky
-// path (the common one) without waiting; marg_collect waits, re-does the tail through the eigen-solver if the device
-// reported that the Cholesky path does not apply, and hands the prior out.
-// status words of a marginalisation (device, 8 ints): [0] singular victim block, [1] support size, [2] Cholesky failed (later: the
-// sweeps of the eigen path), [3] eigenvalue guard failed, [4] the eigen path was taken, [5] the support size km_jacobi sees
-// (round 5: the gate -- st[4] = the eigen path is needed, st[5] = its support size -- is the tail of km_chol, marg_kernels.hip.h)
+// Marginalisation in two halves.  marg_launch stages the problem and queues every kernel and copy without waiting; marg_collect
+// waits for them and hands the prior out.  Which factorisation makes the prior is decided on the device (marg_kernels.hip.h):
+// km_chol factors the compacted matrix, expands its factor into the full-size prior and ends with the gate; km_jacobi behind it is
+// an empty launch unless the gate asks for the eigen path, and then expands its own factor over km_chol's.
+// Status words of a marginalisation (device, 8 ints):
+//   [0] singular victim block                 [1] support size (km_support)
+//   [2] km_chol: the factorisation failed or does not fit -- replaced by the sweep count of km_jacobi when that runs
+//   [3] km_chol: the eigenvalue guard failed
+//   [4] the gate: the eigen path is needed    [5] the gate: the support size km_jacobi sees (0 when [4] is 0)
+// Invariant at the gate: status[4] == (status[2] || status[3]).  The host therefore never has to start the eigen path itself; what
+// it can still see of the invariant after km_jacobi has reused word 2 -- [4] clear means [2] and [3] clear -- marg_collect checks.
 
 static int marg_launch(xrhip_ba *c, const xrhip_marg_problem *M) {
     if (c->marg.pending) return xr_fail(XRHIP_ESTATE, "xrhip_ba_marginalize: a marginalisation is already in flight");
@@ -1455,39 +1419,9 @@ static int marg_launch(xrhip_ba *c, const xrhip_marg_problem *M) {
         return xr_fail(XRHIP_EINVAL, "xrhip_ba_marginalize: bad frame count / victim");
     // express the marginalisation's linearisation as a BA problem with every block free and no robust loss
     const int K = M->n_frames;
-    std::vector<double> state(M->frame_state, M->frame_state + 16 * (size_t)K);
-    std::vector<uint8_t> fix(K, 0);
-    std::vector<double> depth(M->inv_depth, M->inv_depth + std::max(M->n_landmarks, 0));
-    std::vector<uint8_t> lfix(std::max(M->n_landmarks, 1), 0);
-    xrhip_ba_problem P;
-    std::memset(&P, 0, sizeof(P));
-    P.n_frames = K;
-    P.frame_state = state.data();
-    P.frame_fix = fix.data();
-    std::memcpy(P.cam_q_bc, M->cam_q_bc, sizeof(P.cam_q_bc));
-    std::memcpy(P.cam_p_bc, M->cam_p_bc, sizeof(P.cam_p_bc));
-    std::memcpy(P.imu_q_bi, M->imu_q_bi, sizeof(P.imu_q_bi));
-    std::memcpy(P.imu_p_bi, M->imu_p_bi, sizeof(P.imu_p_bi));
-    std::memcpy(P.sqrt_inv_cov, M->sqrt_inv_cov, sizeof(P.sqrt_inv_cov));
-    P.n_landmarks = M->n_landmarks;
-    P.inv_depth = depth.data();
-    P.landmark_fix = lfix.data();
-    P.n_obs = M->n_obs;
-    P.obs_tgt = M->obs_tgt;
-    P.obs_ref = M->obs_ref;
-    P.obs_lm = M->obs_lm;
-    P.obs_z_tgt = M->obs_z_tgt;
-    P.obs_z_ref = M->obs_z_ref;
-    P.n_imu = M->n_imu;
-    P.imu_i = M->imu_i;
-    P.imu_j = M->imu_j;
-    P.imu_data = M->imu_data;
-    P.prior_n = M->prior_n;
-    P.prior_frames = M->prior_frames;
-    P.prior_sqrt_info = M->prior_sqrt_info;
-    P.prior_infovec = M->prior_infovec;
-    P.prior_lin = M->prior_lin;
-    P.max_iterations = 0;
+    std::vector<double> state, depth;
+    std::vector<uint8_t> fix, lfix;
+    const xrhip_ba_problem P = marg_problem_view(*M, state, fix, depth, lfix);
     int rc = validate(&P);
     if (rc) return rc;
     Staged st;
@@ -1499,19 +1433,16 @@ static int marg_launch(xrhip_ba *c, const xrhip_marg_problem *M) {
     d.schur_mode = 0;
     const int N = d.n, R = N - 15;
     if (R > 512) return xr_fail(XRHIP_EINVAL, "xrhip_ba_marginalize: window too large");   // before anything is queued
-    size_t w = 0;
-    const size_t o_Hm = bump256(w, D8 * (size_t)N * N), o_bm = bump256(w, D8 * N), o_T2 = bump256(w, D8 * (size_t)R * 15);
-    const size_t o_A = bump256(w, D8 * (size_t)R * R), o_bp = bump256(w, D8 * R), o_B = bump256(w, D8 * (size_t)R * R);
-    const size_t o_V = bump256(w, D8 * (size_t)R * R), o_si = bump256(w, D8 * (size_t)R * R), o_iv = bump256(w, D8 * R);
-    const size_t o_st = bump256(w, sizeof(int) * 8), o_lam = bump256(w, D8 * 2), o_sup = bump256(w, sizeof(int) * (size_t)R);
-    const size_t o_As = bump256(w, D8 * (size_t)R * R), o_bs = bump256(w, D8 * R), o_Ss = bump256(w, D8 * (size_t)R * R), o_ivs = bump256(w, D8 * R);
-    rc = ensure_work2(c, w + 256, D8 * ((size_t)R * R + R) + 64 + sizeof(int) * 8);
+    const MargScratch o = marg_scratch(N, R);
+    rc = c->work2.reserve(o.bytes, GROW_DOUBLE_1M);
+    if (!rc) rc = c->h_stage.reserve(o.host_bytes, GROW_DOUBLE_1M);
     if (rc) return rc;
-    char *W2 = c->work2;
-    double *Hm = (double *)(W2 + o_Hm), *bm = (double *)(W2 + o_bm), *T2 = (double *)(W2 + o_T2);
-    double *A = (double *)(W2 + o_A), *bp = (double *)(W2 + o_bp), *B = (double *)(W2 + o_B), *V = (double *)(W2 + o_V);
-    double *dsi = (double *)(W2 + o_si), *div = (double *)(W2 + o_iv);
-    int *dst = (int *)(W2 + o_st);
+    char *W2 = c->work2.p;
+    double *Hm = (double *)(W2 + o.Hm), *bm = (double *)(W2 + o.bm), *T2 = (double *)(W2 + o.T2);
+    double *A = (double *)(W2 + o.A), *bp = (double *)(W2 + o.bp), *B = (double *)(W2 + o.B), *V = (double *)(W2 + o.V);
+    double *dsi = (double *)(W2 + o.si), *div = (double *)(W2 + o.iv), *lam = (double *)(W2 + o.lam);
+    double *As = (double *)(W2 + o.As), *bs = (double *)(W2 + o.bs), *Ss = (double *)(W2 + o.Ss), *ivs = (double *)(W2 + o.ivs);
+    int *dst = (int *)(W2 + o.st), *dsn = dst + 1, *dsup = (int *)(W2 + o.sup);
     hipStream_t s = c->stream;
     XR_HIP(hipMemsetAsync(dst, 0, sizeof(int) * 8, s));
     if (d.np) launch_prior_lambda(st, s);
@@ -1523,26 +1454,15 @@ static int marg_launch(xrhip_ba *c, const xrhip_marg_problem *M) {
     hipLaunchKernelGGL(km_permute, dim3((N * N + 255) / 256), dim3(256), 0, s, d, p, M->victim, Hm, bm);
     hipLaunchKernelGGL(km_victim, dim3(1), dim3(256), 0, s, N, Hm, T2, dst);
     hipLaunchKernelGGL(km_complement, dim3((R * R + 255) / 256), dim3(256), 0, s, N, Hm, bm, T2, A, bp);
-    double *hs = (double *)c->h_stage;
-    int *dsup = (int *)(W2 + o_sup), *dsn = dst + 1;
-    double *As = (double *)(W2 + o_As), *bs = (double *)(W2 + o_bs), *Ss = (double *)(W2 + o_Ss), *ivs = (double *)(W2 + o_ivs);
     const int lds_doubles = c->lds_limit / (int)D8;
     hipLaunchKernelGGL(km_support, dim3(1), dim3(512), 0, s, R, A, bp, dsup, dsn, As, bs);
-    // fast path: Cholesky factor of the compacted matrix as sqrt_info (valid when no eigenvalue is near the 1e-8 floor)
-    hipLaunchKernelGGL(km_chol, dim3(1), dim3(512), (size_t)c->lds_limit, s, dsn, lds_doubles, As, bs, dsup, R, dsi, div,
-                       (double *)(W2 + o_lam), dst);
+    hipLaunchKernelGGL(km_chol, dim3(1), dim3(512), (size_t)c->lds_limit, s, dsn, lds_doubles, As, bs, dsup, R, dsi, div, lam, dst);
     XR_HIP(hipGetLastError());
-    // The eigen path (the reference's SelfAdjointEigenSolver route, km_jacobi: milliseconds) is needed when the Cholesky
-    // factor failed or an eigenvalue sits near the 1e-8 floor -- typically the first marginalisation of a sequence.  It used to
-    // be started by the HOST when it collected the result, i.e. on the critical path of the next refine_window.  Now the
-    // device decides: km_chol's tail hands km_jacobi the support size if the fast path's status words ask for the fallback, and 0
-    // otherwise (km_jacobi returns at once on an empty support), so the fallback runs behind the fast path on this context's
-    // own stream like the rest of the marginalisation.  Then one expansion of whichever factor is in place, and the copies.
-    // round 5: km_chol ends with the gate and has already expanded its own factor; km_jacobi (an empty launch unless the gate asks for
-    // it) expands its own -- two launches instead of five behind the factorisation
+    // the eigen path (the reference's SelfAdjointEigenSolver route: milliseconds) -- typically the first marginalisation of a sequence
     hipLaunchKernelGGL(km_jacobi, dim3(1), dim3(1024), (size_t)c->lds_limit, s, dst + 5, lds_doubles, As, bs, B, V, Ss, ivs, 60, dst + 2,
                        dsup, R, dsi, div);
     XR_HIP(hipGetLastError());
+    double *hs = (double *)c->h_stage.p;
     XR_HIP(hipMemcpyAsync(hs, dsi, D8 * (size_t)R * R, hipMemcpyDeviceToHost, s));
     XR_HIP(hipMemcpyAsync(hs + (size_t)R * R, div, D8 * R, hipMemcpyDeviceToHost, s));
     XR_HIP(hipMemcpyAsync(hs + (size_t)R * R + R, dst, sizeof(int) * 8, hipMemcpyDeviceToHost, s));
@@ -1555,16 +1475,7 @@ static int marg_launch(xrhip_ba *c, const xrhip_marg_problem *M) {
     mp.R = R;
     mp.lin.assign(M->frame_state, M->frame_state + 16 * (size_t)K);
     mp.dst = dst;
-    mp.dsup = dsup;
-    mp.lam = (double *)(W2 + o_lam);
-    mp.As = As;
-    mp.bs = bs;
-    mp.B = B;
-    mp.V = V;
-    mp.Ss = Ss;
-    mp.ivs = ivs;
-    mp.dsi = dsi;
-    mp.div = div;
+    mp.lam = lam;
     return XRHIP_OK;
 }
 
@@ -1572,10 +1483,8 @@ static int marg_collect(xrhip_ba *c, double *out_sqrt_info, double *out_infovec,
     xrhip_ba::MargPending &mp = c->marg;
     if (!mp.pending) return xr_fail(XRHIP_ESTATE, "xrhip_ba_marginalize_end: nothing in flight");
     mp.pending = false;
-    hipStream_t s = c->stream;
-    const size_t D8 = sizeof(double);
     const int R = mp.R, K = mp.K;
-    double *hs = (double *)c->h_stage;
+    const double *hs = (const double *)c->h_stage.p;
     XR_HIP(hipEventSynchronize(c->ev_marg));
     int hst[8];
     std::memcpy(hst, hs + (size_t)R * R + R, sizeof(hst));
@@ -1583,20 +1492,8 @@ static int marg_collect(xrhip_ba *c, double *out_sqrt_info, double *out_infovec,
     if (hst[4] && std::getenv("XRHIP_HOSTPROF"))
         std::fprintf(stderr, "[hostprof] marginalisation took the eigen path on the device: guard %s, support %d of %d, %d sweeps\n",
                      hst[3] ? "failed" : "ok", hst[1], R, hst[2]);
-    if ((hst[2] != 0 || hst[3] != 0) && !hst[4]) {   // (not reached: the gate kernel has made this decision on the device)
-        if (std::getenv("XRHIP_HOSTPROF"))
-            std::fprintf(stderr, "[hostprof] marginalisation falls back to the eigen path: cholesky %s, guard %s, support %d of %d\n",
-                         hst[2] ? "failed" : "ok", hst[3] ? "failed" : "ok", hst[1], R);
-        const int lds_doubles = c->lds_limit / (int)D8;
-        int *dsn = mp.dst + 1;
-        hipLaunchKernelGGL(km_jacobi, dim3(1), dim3(1024), (size_t)c->lds_limit, s, dsn, lds_doubles, mp.As, mp.bs, mp.B, mp.V, mp.Ss,
-                           mp.ivs, 60, mp.dst + 2);
-        hipLaunchKernelGGL(km_expand, dim3((R * R + 255) / 256), dim3(256), 0, s, R, mp.dsup, dsn, mp.Ss, mp.ivs, mp.dsi, mp.div);
-        XR_HIP(hipGetLastError());
-        XR_HIP(hipMemcpyAsync(hs, mp.dsi, D8 * (size_t)R * R, hipMemcpyDeviceToHost, s));
-        XR_HIP(hipMemcpyAsync(hs + (size_t)R * R, mp.div, D8 * R, hipMemcpyDeviceToHost, s));
-        XR_HIP(hipStreamSynchronize(s));
-    }
+    if ((hst[2] || hst[3]) && !hst[4])
+        return xr_fail(XRHIP_ESTATE, "xrhip_ba_marginalize: the Cholesky path failed and the device did not take the eigen path");
     std::memcpy(out_sqrt_info, hs, D8 * (size_t)R * R);
     std::memcpy(out_infovec, hs + (size_t)R * R, D8 * R);
     int j = 0;
@@ -1645,16 +1542,11 @@ static int preint_stage(xrhip_ba *c, const double *samples, const int *sample_be
     // addresses directly over the host link -- an integration moves a few hundred bytes in and 2.2 KB out, so
     // copy-engine round trips (H2D, memset, D2H) would cost several times the kernel itself.  Each job's status word
     // is its completion mailbox.
-    const size_t b_jobs = sizeof(PreintJob) * n_jobs, b_smp = D8 * 7 * (size_t)total, b_noise = D8 * 36;
-    const size_t b_out = D8 * XRHIP_IMU_DIM * (size_t)n_jobs, b_st = 2 * sizeof(int) * n_jobs;   // status words, then the early-delta words
-    size_t used = 0;
-    const size_t o_jobs = bump256(used, b_jobs), o_smp = bump256(used, b_smp), o_noise = bump256(used, b_noise);
-    const size_t o_out = bump256(used, b_out + b_st), o_st = o_out + b_out;   // (the status words follow the results directly)
-    const size_t bytes = used + 256;
-    int rc = ensure_work2(c, 0, bytes);
+    const PreintScratch o = preint_scratch(n_jobs, total);
+    int rc = c->h_stage.reserve(o.bytes, GROW_DOUBLE_1M);
     if (rc) return rc;
-    char *H = c->h_stage;
-    PreintJob *jobs = (PreintJob *)(H + o_jobs);
+    char *H = c->h_stage.p;
+    PreintJob *jobs = (PreintJob *)(H + o.jobs);
     for (int k = 0; k < n_jobs; ++k) {
         jobs[k].sample_begin = sample_begin[k];
         jobs[k].sample_count = sample_count[k];
@@ -1666,24 +1558,20 @@ static int preint_stage(xrhip_ba *c, const double *samples, const int *sample_be
         jobs[k].bias_frame = bias_frame ? bias_frame[k] : -1;
         jobs[k].pad_ = 0;
     }
-    std::memcpy(H + o_smp, samples, b_smp);
-    std::memcpy(H + o_noise, noise_cov36, b_noise);
-    std::memset(H + o_st, 0, 2 * sizeof(int) * n_jobs);
-    c->preint_o_jobs = o_jobs;
-    c->preint_o_smp = o_smp;
-    c->preint_o_noise = o_noise;
-    c->preint_o_out = o_out;
-    c->preint_o_st = o_st;
+    std::memcpy(H + o.smp, samples, D8 * 7 * (size_t)total);
+    std::memcpy(H + o.noise, noise_cov36, D8 * 36);
+    std::memset(H + o.st, 0, 2 * sizeof(int) * n_jobs);
+    c->preint_o = o;
     return XRHIP_OK;
 }
 
 static int preint_args(xrhip_ba *c, int n_jobs, int jac, int cov, const double *state_dev, PreintArgs *a) {
     char *Dv = nullptr;
-    XR_HIP(hipHostGetDevicePointer((void **)&Dv, c->h_stage, 0));
-    *a = PreintArgs{(const PreintJob *)(Dv + c->preint_o_jobs), (const double *)(Dv + c->preint_o_smp), (const double *)(Dv + c->preint_o_noise),
-                    jac ? 1 : 0, cov ? 1 : 0, (double *)(Dv + c->preint_o_out), (int *)(Dv + c->preint_o_st),
-                    (int *)(Dv + c->preint_o_st) + n_jobs, state_dev, n_jobs, {}};
-    const PreintJob *hj = (const PreintJob *)(c->h_stage + c->preint_o_jobs);
+    XR_HIP(hipHostGetDevicePointer((void **)&Dv, c->h_stage.p, 0));
+    *a = PreintArgs{(const PreintJob *)(Dv + c->preint_o.jobs), (const double *)(Dv + c->preint_o.smp), (const double *)(Dv + c->preint_o.noise),
+                    jac ? 1 : 0, cov ? 1 : 0, (double *)(Dv + c->preint_o.out), (int *)(Dv + c->preint_o.st),
+                    (int *)(Dv + c->preint_o.st) + n_jobs, state_dev, n_jobs, {}};
+    const PreintJob *hj = (const PreintJob *)(c->h_stage.p + c->preint_o.jobs);
     for (int k = 0; k < std::min(n_jobs, PI_HEAD); ++k) a->head[k] = hj[k];
     return XRHIP_OK;
 }
@@ -1734,7 +1622,7 @@ static int preint_launch_deferred(xrhip_ba *c, const xrhip_ba_problem *P, const 
     const int rc = preint_deferred_check(c, P);
     if (rc) return rc;
     const int n_jobs = c->preint_deferred;
-    PreintJob *jobs = (PreintJob *)(c->h_stage + c->preint_o_jobs);
+    PreintJob *jobs = (PreintJob *)(c->h_stage.p + c->preint_o.jobs);
     for (int k = 0; k < n_jobs; ++k) {
         const int f = jobs[k].bias_frame;
         if (!state_dev) {
@@ -1788,9 +1676,9 @@ int xrhip_ba_preintegrate_early(xrhip_ba *c, int job, double *out_delta11) {
     if (!c || !out_delta11 || job < 0) return xr_fail(XRHIP_EINVAL, "xrhip_ba_preintegrate_early: bad arguments");
     if (!c->preint_pending || job >= c->preint_pending)
         return xr_fail(XRHIP_ESTATE, "xrhip_ba_preintegrate_early: no such job in flight");
-    char *H = c->h_stage;
+    char *H = c->h_stage.p;
     const int n_jobs = c->preint_pending;
-    volatile int *early = (volatile int *)(H + c->preint_o_st) + n_jobs;
+    volatile int *early = (volatile int *)(H + c->preint_o.st) + n_jobs;
     if (c->preint_rq) {
         const int rc = group_wait_launched(c->preint_rq);
         if (rc) return rc;
@@ -1801,7 +1689,7 @@ int xrhip_ba_preintegrate_early(xrhip_ba *c, int job, double *out_delta11) {
             if (q == hipSuccess && early[job] == 0) return xr_fail(XRHIP_ESTATE, "xrhip_ba_preintegrate_early: kernel retired without publishing");
             if (q != hipSuccess && q != hipErrorNotReady) return xr_fail(XRHIP_EHIP, "xrhip_ba_preintegrate_early: stream error");
         }
-    std::memcpy(out_delta11, H + c->preint_o_out + sizeof(double) * XRHIP_IMU_DIM * (size_t)job, sizeof(double) * 11);
+    std::memcpy(out_delta11, H + c->preint_o.out + sizeof(double) * XRHIP_IMU_DIM * (size_t)job, sizeof(double) * 11);
     return XRHIP_OK;
 }
 
@@ -1814,8 +1702,8 @@ int xrhip_ba_preintegrate_end(xrhip_ba *c, double *out) {
     if (!c->preint_pending) return xr_fail(XRHIP_ESTATE, "xrhip_ba_preintegrate_end: nothing in flight");
     const int n_jobs = c->preint_pending;
     c->preint_pending = 0;
-    char *H = c->h_stage;
-    volatile int *st = (volatile int *)(H + c->preint_o_st);
+    char *H = c->h_stage.p;
+    volatile int *st = (volatile int *)(H + c->preint_o.st);
     if (c->preint_rq) {   // grouped: the stream below is shared -- idle says nothing before the request has been launched
         const int rc = group_wait_launched(c->preint_rq);
         if (rc) return rc;
@@ -1829,7 +1717,7 @@ int xrhip_ba_preintegrate_end(xrhip_ba *c, double *out) {
             }
     for (int k = 0; k < n_jobs; ++k)
         if (st[k] != 1) return xr_fail(XRHIP_ESTATE, "xrhip_ba_preintegrate: covariance is not positive definite");
-    std::memcpy(out, H + c->preint_o_out, sizeof(double) * XRHIP_IMU_DIM * (size_t)n_jobs);
+    std::memcpy(out, H + c->preint_o.out, sizeof(double) * XRHIP_IMU_DIM * (size_t)n_jobs);
     return XRHIP_OK;
 }
 

@@ -1,12 +1,17 @@
 // ba_stage.hpp -- the device layout of one staged bundle-adjustment problem, written down ONCE.
 // stage_index() builds the gather tables on the host; XRHIP_BA_LAYOUT lists every buffer of the input arena and of the device workspace
 // with its size; offsets and totals, the BaPtrs of a solve, the copies into the pinned arena, the second pointer set of a speculative
-// linearisation and the exchange of the two sets are all expansions of that one list.  ba_api.hip keeps what needs the HIP runtime.
+// linearisation and the exchange of the two sets are all expansions of that one list.  Behind it the three scratch layouts that are
+// not a staged problem's -- marg_scratch (marginalisation, work2), cov_scratch (xrhip_ba_covariance) and preint_scratch (the pinned
+// block of a pre-integration batch) -- and marg_problem_view, the marginalisation's factors as a BA problem.  ba_api.hip keeps what
+// needs the HIP runtime.
 // Host only, no C ABI: tests/host_check/ba_stage_host.cpp pins offsets, sets and tables without a GPU (tests/test_ba_stage_host.py).
 #pragma once
 #include "../../include/xrslam_hip.h"
 #include "ba_kernels.hip.h"
 #include "ba_plan.hpp"
+#include "marg_kernels.hip.h"   // PreintJob
+#include "cov_kernels.hip.h"    // CovStatus (after marg_kernels.hip.h, as ba_api.hip includes them: the order is part of the build)
 
 #include <algorithm>
 #include <cstdint>
@@ -284,6 +289,115 @@ inline void swap_lin_sets(BaPtrs &p, BaPtrs &p2) {
 #define XRHIP_LIN(m, bytes) std::swap(p.m, p2.m);
     XRHIP_BA_LAYOUT(XRHIP_BA_SKIP, XRHIP_BA_SKIP, XRHIP_LIN)
 #undef XRHIP_LIN
+}
+
+// ---------------------------------------------------------------------------------------------- scratch layouts
+// Offsets into one block each, bumped in member order; `bytes` is what the block must hold.  Frozen like the list above.
+struct MargScratch {   // device (work2); N = 15 K unknowns, R = N - 15 of them stay
+    size_t Hm, bm, T2, A, bp, B, V, si, iv, st, lam, sup, As, bs, Ss, ivs, bytes;
+    size_t host_bytes;   // pinned readback: sqrt_info [R x R], infovec [R], the eight status words
+};
+inline MargScratch marg_scratch(int N, int R) {
+    const size_t n = (size_t)N, r = (size_t)R;
+    size_t w = 0;
+    MargScratch m;
+    m.Hm = bump256(w, D8 * n * n);
+    m.bm = bump256(w, D8 * n);
+    m.T2 = bump256(w, D8 * r * 15);
+    m.A = bump256(w, D8 * r * r);
+    m.bp = bump256(w, D8 * r);
+    m.B = bump256(w, D8 * r * r);
+    m.V = bump256(w, D8 * r * r);
+    m.si = bump256(w, D8 * r * r);
+    m.iv = bump256(w, D8 * r);
+    m.st = bump256(w, sizeof(int) * 8);
+    m.lam = bump256(w, D8 * 2);
+    m.sup = bump256(w, sizeof(int) * r);
+    m.As = bump256(w, D8 * r * r);
+    m.bs = bump256(w, D8 * r);
+    m.Ss = bump256(w, D8 * r * r);
+    m.ivs = bump256(w, D8 * r);
+    m.bytes = w + 256;
+    m.host_bytes = D8 * (r * r + r) + 64 + sizeof(int) * 8;
+    return m;
+}
+
+struct CovScratch {   // device (cov_dev)
+    size_t st, A, Li, ds, cols, B, Sig, out, var, bytes;
+};
+// n16: the reduced system's order padded to 16, nt = n16 / 16; groups: right-hand-side groups of 16 columns in B; full: the whole
+// inverse is kept (Sig; an 8-byte stand-in otherwise); L: landmarks
+inline CovScratch cov_scratch(int n16, int nt, int n_sel, int groups, bool full, int L) {
+    size_t w = 0;
+    CovScratch s;
+    s.st = bump256(w, sizeof(CovStatus));
+    s.A = bump256(w, D8 * (size_t)n16 * n16);
+    s.Li = bump256(w, D8 * 256 * (size_t)nt);
+    s.ds = bump256(w, D8 * n16);
+    s.cols = bump256(w, sizeof(int) * 16 * (size_t)(n_sel + nt));
+    s.B = bump256(w, D8 * 16 * (size_t)n16 * std::max(groups, 1));
+    s.Sig = bump256(w, full ? D8 * (size_t)n16 * n16 : 8);
+    s.out = bump256(w, D8 * 225 * (size_t)std::max(n_sel, 1));
+    s.var = bump256(w, D8 * std::max(L, 1));
+    s.bytes = w + 256;
+    return s;
+}
+
+struct PreintScratch {   // pinned host (h_stage), addressed by the kernel over the host link
+    size_t jobs, smp, noise, out, st, bytes;
+};
+inline PreintScratch preint_scratch(int n_jobs, int total_samples) {
+    const size_t b_out = D8 * XRHIP_IMU_DIM * (size_t)n_jobs, b_st = 2 * sizeof(int) * n_jobs;   // status words, then the early-delta words
+    size_t w = 0;
+    PreintScratch s;
+    s.jobs = bump256(w, sizeof(PreintJob) * n_jobs);
+    s.smp = bump256(w, D8 * 7 * (size_t)total_samples);
+    s.noise = bump256(w, D8 * 36);
+    s.out = bump256(w, b_out + b_st);
+    s.st = s.out + b_out;   // (the status words follow the results directly)
+    s.bytes = w + 256;
+    return s;
+}
+
+// The marginalisation's linearisation as a BA problem: every block free, no iteration.  state / fix / depth / lfix are the caller's
+// and receive the copies the problem points at (they must outlive its staging).
+inline xrhip_ba_problem marg_problem_view(const xrhip_marg_problem &M, std::vector<double> &state, std::vector<uint8_t> &fix,
+                                          std::vector<double> &depth, std::vector<uint8_t> &lfix) {
+    const int K = M.n_frames;
+    state.assign(M.frame_state, M.frame_state + 16 * (size_t)K);
+    fix.assign(K, 0);
+    depth.assign(M.inv_depth, M.inv_depth + std::max(M.n_landmarks, 0));
+    lfix.assign(std::max(M.n_landmarks, 1), 0);
+    xrhip_ba_problem P;
+    std::memset(&P, 0, sizeof(P));
+    P.n_frames = K;
+    P.frame_state = state.data();
+    P.frame_fix = fix.data();
+    std::memcpy(P.cam_q_bc, M.cam_q_bc, sizeof(P.cam_q_bc));
+    std::memcpy(P.cam_p_bc, M.cam_p_bc, sizeof(P.cam_p_bc));
+    std::memcpy(P.imu_q_bi, M.imu_q_bi, sizeof(P.imu_q_bi));
+    std::memcpy(P.imu_p_bi, M.imu_p_bi, sizeof(P.imu_p_bi));
+    std::memcpy(P.sqrt_inv_cov, M.sqrt_inv_cov, sizeof(P.sqrt_inv_cov));
+    P.n_landmarks = M.n_landmarks;
+    P.inv_depth = depth.data();
+    P.landmark_fix = lfix.data();
+    P.n_obs = M.n_obs;
+    P.obs_tgt = M.obs_tgt;
+    P.obs_ref = M.obs_ref;
+    P.obs_lm = M.obs_lm;
+    P.obs_z_tgt = M.obs_z_tgt;
+    P.obs_z_ref = M.obs_z_ref;
+    P.n_imu = M.n_imu;
+    P.imu_i = M.imu_i;
+    P.imu_j = M.imu_j;
+    P.imu_data = M.imu_data;
+    P.prior_n = M.prior_n;
+    P.prior_frames = M.prior_frames;
+    P.prior_sqrt_info = M.prior_sqrt_info;
+    P.prior_infovec = M.prior_infovec;
+    P.prior_lin = M.prior_lin;
+    P.max_iterations = 0;
+    return P;
 }
 
 }   // namespace xrhip

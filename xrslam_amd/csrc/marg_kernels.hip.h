@@ -1,9 +1,9 @@
 // marg_kernels.hip.h -- gfx950 kernels for keyframe marginalisation and IMU pre-integration.
 //
 // Replaces CeresMarginalizationFactor::marginalize
-//   (/root/reference/xrslam/src/xrslam/estimation/ceres/marginalization_factor.h:74-475)
+//   (xrslam/src/xrslam/estimation/ceres/marginalization_factor.h:74-475)
 // and PreIntegrator::integrate / increment / compute_sqrt_inv_cov
-//   (/root/reference/xrslam/src/xrslam/estimation/preintegrator.cpp:22-100).
+//   (xrslam/src/xrslam/estimation/preintegrator.cpp:22-100).
 //
 // Marginalisation pipeline (the linearisation and the landmark Schur product reuse the BA
 // kernels with the robust loss switched off):
@@ -11,8 +11,11 @@
 //   km_permute     landmark-reduced system with the victim frame moved last
 //   km_victim      15x15 inverse of the victim block (pivoted Gauss-Jordan in LDS), T2 = H_rv H_vv^-1
 //   km_complement  H' = H_rr - T2 H_vr, b' = b_r - T2 b_v, lower triangle mirrored
-//   km_jacobi      symmetric eigen-decomposition by parallel one-sided Jacobi (round-robin pairs)
-//   km_finish      sqrt_info = diag(sqrt(lambda)) V^T, infovec = diag(1/sqrt(lambda)) V^T b' (lambda <= 1e-8 -> 0)
+//   km_support     the rows / columns of H' that are not exactly zero, compacted
+//   km_chol        Cholesky factor of the compacted matrix as the prior, its eigenvalue guard, and the gate: is the eigen path needed
+//   km_jacobi      the eigen path, device-gated (an empty launch unless the gate asks): symmetric eigen-decomposition by parallel
+//                  one-sided Jacobi, sqrt_info = diag(sqrt(lambda)) V^T, infovec = diag(1/sqrt(lambda)) V^T b' (lambda <= 1e-8 -> 0)
+// km_chol and km_jacobi each expand their own compact factor into the full-size prior; there is no other route to it.
 #pragma once
 #include "ba_kernels.hip.h"
 #include "dense_lds.hip.h"
@@ -207,34 +210,6 @@ __global__ __launch_bounds__(512) void km_support(int R, const double *__restric
     for (int i = tid; i < Rs; i += nt) bs[i] = bp[idx[i]];
 }
 
-// scatter the compact factor back: sqrt_info [R x R] (zero outside the support), infovec [R]
-__global__ __launch_bounds__(256) void km_expand(int R, const int *__restrict__ sup_idx, const int *__restrict__ sup_n,
-                                                 const double *__restrict__ Ss, const double *__restrict__ ivs,
-                                                 double *__restrict__ sqrt_info, double *__restrict__ infovec) {
-    const int Rs = *sup_n;
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= R * R) return;
-    const int i = e / R, j = e - i * R;
-    // row i of the full factor = row i of the compact factor (rows >= Rs are zero), columns scattered
-    double v = 0.0;
-    if (i < Rs) {
-        // find j in the support (sup_idx ascending): binary search
-        int lo = 0, hi = Rs - 1;
-        while (lo <= hi) {
-            const int mid = (lo + hi) >> 1;
-            const int sj = sup_idx[mid];
-            if (sj == j) {
-                v = Ss[(size_t)i * Rs + mid];
-                break;
-            }
-            if (sj < j) lo = mid + 1;
-            else hi = mid - 1;
-        }
-    }
-    sqrt_info[e] = v;
-    if (j == 0) infovec[i] = (i < Rs) ? ivs[i] : 0.0;
-}
-
 // Parallel one-sided (Hestenes) Jacobi on the symmetric matrix A: B = A V is driven to orthogonal columns by
 // plane rotations applied to column pairs; the R/2 pairs of a round-robin round are disjoint and processed
 // concurrently by G-thread groups.  B, V are column-major R x R (LDS when they fit, else L2-resident global).
@@ -307,15 +282,16 @@ __device__ __forceinline__ int jacobi_sweeps(int R, int G, double *B, double *V,
     return sweep;
 }
 
-// Eigen-decomposition of the compacted matrix As (Rs = *sup_n).  use_lds: B and V live in dynamic LDS
-// (2 Rs^2 doubles must fit, checked on the device), otherwise in the global buffers Bg, Vg.
-// Outputs the compact factor: Ss row i = sqrt(lambda_i) v_i^T, ivs_i = v_i . bs / sqrt(lambda_i), lambda <= 1e-8 dropped.
+// Eigen-decomposition of the compacted matrix As (Rs = *sup_n; 0: nothing to do, the launch is empty).  B and V live in dynamic LDS
+// when 2 Rs^2 doubles fit (checked on the device), otherwise in the global buffers Bg, Vg.
+// Outputs the compact factor: Ss row i = sqrt(lambda_i) v_i^T, ivs_i = v_i . bs / sqrt(lambda_i), lambda <= 1e-8 dropped, and its
+// expansion into the full-size prior (sqrt_info_full [Rf x Rf], zero outside the support; infovec_full [Rf]).
 __global__ __launch_bounds__(1024) void km_jacobi(const int *__restrict__ sup_n, int lds_doubles,
                                                   const double *__restrict__ As, const double *__restrict__ bs,
                                                   double *__restrict__ Bg, double *__restrict__ Vg,
                                                   double *__restrict__ Ss, double *__restrict__ ivs, int max_sweeps,
-                                                  int *__restrict__ sweeps_out, const int *__restrict__ sup_idx = nullptr, int Rf = 0,
-                                                  double *__restrict__ sqrt_info_full = nullptr, double *__restrict__ infovec_full = nullptr) {
+                                                  int *__restrict__ sweeps_out, const int *__restrict__ sup_idx, int Rf,
+                                                  double *__restrict__ sqrt_info_full, double *__restrict__ infovec_full) {
     extern __shared__ double lds[];
     __shared__ int rotated;
     const int R = *sup_n;
@@ -349,42 +325,41 @@ __global__ __launch_bounds__(1024) void km_jacobi(const int *__restrict__ sup_n,
         for (int e = lane; e < R; e += 64) Ss[(size_t)i * R + e] = sl * v[e];
         if (lane == 0) ivs[i] = sli * vb;
     }
-    // round 5: the expansion into the full-size prior (km_expand's scatter) in the same launch -- this kernel runs once per sequence
-    if (sqrt_info_full) {
-        __threadfence_block();
-        __syncthreads();
-        for (int e = tid; e < Rf * Rf; e += nt) {
-            const int i = e / Rf, j = e - i * Rf;
-            double v = 0.0;
-            if (i < R) {
-                int lo = 0, hi = R - 1;
-                while (lo <= hi) {
-                    const int mid = (lo + hi) >> 1;
-                    const int sj = sup_idx[mid];
-                    if (sj == j) {
-                        v = Ss[(size_t)i * R + mid];
-                        break;
-                    }
-                    if (sj < j) lo = mid + 1;
-                    else hi = mid - 1;
+    // the expansion into the full-size prior, in the same launch: row i of the full factor = row i of the compact one (rows >= R are
+    // zero), its columns scattered over the support (sup_idx ascending: binary search)
+    __threadfence_block();
+    __syncthreads();
+    for (int e = tid; e < Rf * Rf; e += nt) {
+        const int i = e / Rf, j = e - i * Rf;
+        double v = 0.0;
+        if (i < R) {
+            int lo = 0, hi = R - 1;
+            while (lo <= hi) {
+                const int mid = (lo + hi) >> 1;
+                const int sj = sup_idx[mid];
+                if (sj == j) {
+                    v = Ss[(size_t)i * R + mid];
+                    break;
                 }
+                if (sj < j) lo = mid + 1;
+                else hi = mid - 1;
             }
-            sqrt_info_full[e] = v;
         }
-        for (int i = tid; i < Rf; i += nt) infovec_full[i] = i < R ? ivs[i] : 0.0;
+        sqrt_info_full[e] = v;
     }
+    for (int i = tid; i < Rf; i += nt) infovec_full[i] = i < R ? ivs[i] : 0.0;
 }
 
 // Cholesky fast path of "create marginalization factor" (marginalization_factor.h:440-455).  When every
 // eigenvalue of the marginal information matrix A exceeds the reference's 1e-8 floor, no eigen-direction is
 // dropped and ANY factor S with S^T S = A carries the same prior: S = L^T (A = L L^T), infovec = L^-1 b'
 // reproduce Lambda = S^T S and eta = S^T infovec exactly like diag(sqrt(lambda)) V^T would.  The kernel
-// factors A in LDS and bounds lambda_min from above by inverse iteration; the caller falls back to the
-// Jacobi eigen-solver (km_jacobi) when the factorisation fails or the bound is not comfortably above the floor.
-// Round 5: the guard's inverse is blocked (tri_inverse_blocked, matrix cores) instead of one forward substitution per thread; the kernel
-// also takes over what three launches behind it did on 26 of 27 marginalisations -- the gate (status[4], status[5]: does the eigen path
-// have to run, and on what support) and the expansion of its own factor into the full-size prior (km_expand's scatter, straight from
-// LDS) -- so that in steady state km_jacobi is one empty launch behind this one and nothing else.
+// factors A in LDS, expands the factor into the full-size prior (straight from LDS) and bounds lambda_min (the guard, below).
+// The kernel ends with the gate.  fast = the factorisation stood and the guard passed; every path that sets status[2] (no factor)
+// or status[3] (guard failed) returns fast = false, and no other does, so
+//     status[4] = !fast = (status[2] || status[3])   the eigen path is needed
+//     status[5] = fast ? 0 : R                       the support size km_jacobi, launched behind this kernel, reads as its order
+// In steady state km_jacobi is therefore one empty launch; when it runs it writes its own expansion over this kernel's.
 __device__ __forceinline__ bool km_chol_body(int R, int lds_doubles, const double *__restrict__ A, const double *__restrict__ bp,
                                              const int *__restrict__ sup_idx, int Rf, double *__restrict__ sqrt_info_full,
                                              double *__restrict__ infovec_full, double *__restrict__ lam_est, int *__restrict__ status,
@@ -476,7 +451,7 @@ __global__ __launch_bounds__(512) void km_chol(const int *__restrict__ sup_n, in
     const int R = *sup_n;
     const bool fast = km_chol_body(R, lds_doubles, A, bp, sup_idx, Rf, sqrt_info_full, infovec_full, lam_est, status, lds, Dblk, scratch,
                                    &fail, s_pos);
-    // the gate (round 2's kx_marg_gate): the eigen path runs on the support iff the fast path does not stand
+    // the gate: the eigen path runs on the support iff the fast path does not stand
     if (threadIdx.x == 0) {
         status[4] = fast ? 0 : 1;
         status[5] = fast ? 0 : R;
