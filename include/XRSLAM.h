@@ -164,7 +164,12 @@ void XRSLAMAmdPushImageDeviceColor(const void *pixels_dev, int stride, int chann
  *   YUYV / UYVY     packed 4:2:2, the Y byte of each pixel's pair (byte 0 / byte 1)
  *   NV12 / I420     the luma plane: `stride` is that plane's, and only its `height` rows are read (push a decoder's surface as is)
  *   P010            the high byte of the luma plane's 16-bit samples; only `height` rows of that plane are read
- * limited_range (video levels, luma 16..235; not for the four RGB / BGR formats): gray' = min(255, ((max(gray,16) - 16) * 255 + 109) / 219).
+ *   BAYER_*8 / *16  a raw colour-filter mosaic of 8-bit / little-endian 16-bit samples (`bits` as GRAY16).  The name is the frame's
+ *                   top-left 2 x 2 tile read row by row (RGGB: (0,0) red, (1,0) green, (0,1) green, (1,1) blue -- the GenICam / V4L2 /
+ *                   ROS bayer_* convention; OpenCV's COLOR_Bayer* names are shifted by one pixel against it).  Demosaiced bilinearly,
+ *                   neighbours mirrored at the frame's (a scaled frame: the crop's) edges, and weighted like BGR8, in exact integer
+ *                   arithmetic with one rounding (include/xrslam_hip.h has the formula); a constant mosaic gives that constant
+ * limited_range (video levels, luma 16..235; not for the RGB / BGR and Bayer formats): gray' = min(255, ((max(gray,16) - 16) * 255 + 109) / 219).
  * Any base alignment, any stride >= width * bytes per pixel.  With device undistortion on: reduced first, rectified second.  A bad
  * format, bits, stride or flag drops the frame and sets XRSLAMAmdLastError; nothing aborts. */
 typedef enum XRSLAMAmdPixelFormat {
@@ -178,11 +183,20 @@ typedef enum XRSLAMAmdPixelFormat {
     XRSLAM_AMD_PIXEL_UYVY,
     XRSLAM_AMD_PIXEL_NV12,
     XRSLAM_AMD_PIXEL_I420,
-    XRSLAM_AMD_PIXEL_P010
+    XRSLAM_AMD_PIXEL_P010,
+    /* (11..15 are not formats) */
+    XRSLAM_AMD_PIXEL_BAYER_RGGB8 = 16,
+    XRSLAM_AMD_PIXEL_BAYER_GRBG8 = 17,
+    XRSLAM_AMD_PIXEL_BAYER_GBRG8 = 18,
+    XRSLAM_AMD_PIXEL_BAYER_BGGR8 = 19,
+    XRSLAM_AMD_PIXEL_BAYER_RGGB16 = 20,
+    XRSLAM_AMD_PIXEL_BAYER_GRBG16 = 21,
+    XRSLAM_AMD_PIXEL_BAYER_GBRG16 = 22,
+    XRSLAM_AMD_PIXEL_BAYER_BGGR16 = 23
 } XRSLAMAmdPixelFormat;
 typedef struct XRSLAMAmdFrameFormat {
     int format;          /* XRSLAMAmdPixelFormat */
-    int bits;            /* GRAY16: significant bits, 8..16; 0 = 16.  Not read for the other formats. */
+    int bits;            /* GRAY16, BAYER_*16: significant bits, 8..16; 0 = 16.  Not read for the other formats. */
     int limited_range;   /* 1: video levels, expanded to 0..255 */
 } XRSLAMAmdFrameFormat;
 void XRSLAMAmdPushImageFormat(const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt, int on_device, double timestamp);

@@ -104,14 +104,37 @@ int xrhip_image_upload_color_distorted(xrhip_image *img, const void *pixels, int
  *   YUYV, UYVY          2 bytes   the Y byte of the pixel's pair: byte 0 / byte 1
  *   NV12, I420          1 byte    the luma plane; stride_bytes is that plane's, and only its `height` rows are read
  *   P010                2 bytes   the high byte of the luma plane's 16-bit sample; only `height` rows of that plane are read
- * `bits` is read for GRAY16 only.  limited_range (video levels, luma 16..235; XRHIP_EINVAL for the four RGB / BGR formats) is applied
+ * `bits` is read for GRAY16 (and BAYER_*16, below) only.  limited_range (video levels, luma 16..235; XRHIP_EINVAL for the four RGB / BGR formats) is applied
  * to the 8-bit value: min(255, ((max(gray, 16) - 16) * 255 + 109) / 219).
  * `pixels`: a host pointer, or an HBM pointer when on_device; any base alignment (an odd address for the 2-byte formats included),
  * any stride_bytes >= width * bytes per pixel.  Of the `height` rows only the first width * bytes-per-pixel bytes are needed: the
  * device reads whole aligned dwords, each of which holds at least one such byte.  Buffer lifetimes, group behaviour and the
  * _distorted form (reduced first, rectified second; XRHIP_ESTATE without a map) are those of xrhip_image_upload_color.  GRAY8
  * without limited_range, BGR8 and BGRA8 forward to the older entry points.  XRHIP_EINVAL (the message names the argument): unknown
- * `format`, `bits` outside 8..16, `stride` too short, `limited_range` with an RGB / BGR format, a null pointer. */
+ * `format`, `bits` outside 8..16, `stride` too short, `limited_range` with an RGB / BGR format, a null pointer.
+ *
+ * Bayer raw mosaics (machine-vision cameras, RealSense raw streams, sensor_msgs/Image bayer_*): one sample per pixel behind a colour
+ * filter, demosaiced to gray as part of the upload.  The name gives the colours of the frame's top-left 2 x 2 tile read row by row:
+ * RGGB means pixel (0,0) is red, (1,0) green, (0,1) green, (1,1) blue -- the GenICam / V4L2 / ROS convention.  (OpenCV's
+ * COLOR_Bayer* names are shifted by one pixel against it: its "BayerBG" is RGGB here, "BayerGB" GRBG, "BayerGR" GBRG, "BayerRG" BGGR.)
+ *   BAYER_*8            1 byte    the sample s is the byte; `bits` is not read
+ *   BAYER_*16           2 bytes   little endian, `bits` significant (8..16, 0 = 16), reduced like GRAY16: s = min(255, v >> (bits - 8))
+ * A pattern is a phase (px, py) of RGGB: GRBG = (1,0), GBRG = (0,1), BGGR = (1,1); the colour site of (x, y) is RGGB's at
+ * ((x + px) & 1, (y + py) & 1).  Neighbours outside the n_x x n_y frame mirror without repeating the edge (-1 -> 1, n -> n - 2), so
+ * every neighbour lies on a site of the colour it stands for.  With s() mirrored that way, at (x, y):
+ *   C = 4 s(x,y)    P = s(x-1,y) + s(x+1,y) + s(x,y-1) + s(x,y+1)    X = the sum of the four diagonal neighbours
+ *   Hh = 2 (s(x-1,y) + s(x+1,y))    Vv = 2 (s(x,y-1) + s(x,y+1))
+ *   red site: R4 = C, G4 = P, B4 = X            green site between reds in its row:  R4 = Hh, G4 = C, B4 = Vv
+ *   blue site: B4 = C, G4 = P, R4 = X           green site between blues in its row: R4 = Vv, G4 = C, B4 = Hh
+ *   gray = (4899 R4 + 9617 G4 + 1868 B4 + 32768) >> 16
+ * -- bilinear demosaicing (each sum is four times the bilinear estimate) followed by the BGR weights, in exact arithmetic with one
+ * rounding: a mosaic of constant value v gives v, nothing exceeds 255, every intermediate fits 32 bits.  No bit parity with OpenCV's
+ * demosaicing is claimed.  limited_range with a Bayer format is XRHIP_EINVAL.  Any base alignment (a 16-bit mosaic at an odd address
+ * included), any stride_bytes >= width * (1 or 2).  A launch of its own in the context's order (k_upload_bayer; a member of a group:
+ * behind its pending shared upload, like the scaled upload); a host frame goes through the pinned slots to an HBM scratch, a frame in
+ * HBM is read where it lies.  xrhip_image_upload_scaled*: the crop is a Bayer frame of its own -- its phase is the source's shifted by
+ * (crop_x & 1, crop_y & 1), neighbours mirror at the crop's edges, only the crop's bytes are read -- and g(i, j) of the area mean is the
+ * Bayer gray of crop pixel (i, j).  Format numbers 11..15 and 24.. are not formats. */
 #define XRHIP_PIXFMT_GRAY8 0
 #define XRHIP_PIXFMT_BGR8 1
 #define XRHIP_PIXFMT_BGRA8 2
@@ -123,6 +146,14 @@ int xrhip_image_upload_color_distorted(xrhip_image *img, const void *pixels, int
 #define XRHIP_PIXFMT_NV12 8
 #define XRHIP_PIXFMT_I420 9
 #define XRHIP_PIXFMT_P010 10
+#define XRHIP_PIXFMT_BAYER_RGGB8 16
+#define XRHIP_PIXFMT_BAYER_GRBG8 17
+#define XRHIP_PIXFMT_BAYER_GBRG8 18
+#define XRHIP_PIXFMT_BAYER_BGGR8 19
+#define XRHIP_PIXFMT_BAYER_RGGB16 20
+#define XRHIP_PIXFMT_BAYER_GRBG16 21
+#define XRHIP_PIXFMT_BAYER_GBRG16 22
+#define XRHIP_PIXFMT_BAYER_BGGR16 23
 int xrhip_image_upload_format(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits, int limited_range,
                               int on_device);
 int xrhip_image_upload_format_distorted(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits,

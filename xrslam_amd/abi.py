@@ -180,6 +180,10 @@ PIXFMT_GRAY8, PIXFMT_BGR8, PIXFMT_BGRA8, PIXFMT_RGB8, PIXFMT_RGBA8, PIXFMT_GRAY1
     PIXFMT_I420, PIXFMT_P010 = range(11)
 PIXFMT_BYTES = {PIXFMT_GRAY8: 1, PIXFMT_BGR8: 3, PIXFMT_BGRA8: 4, PIXFMT_RGB8: 3, PIXFMT_RGBA8: 4, PIXFMT_GRAY16: 2, PIXFMT_YUYV: 2,
                 PIXFMT_UYVY: 2, PIXFMT_NV12: 1, PIXFMT_I420: 1, PIXFMT_P010: 2}   # bytes per pixel read (NV12 / I420 / P010: the luma plane's)
+# Bayer raw mosaics, named by the top-left 2 x 2 tile read row by row (11..15 are not formats); *8: one byte per sample, *16: two
+PIXFMT_BAYER_RGGB8, PIXFMT_BAYER_GRBG8, PIXFMT_BAYER_GBRG8, PIXFMT_BAYER_BGGR8, PIXFMT_BAYER_RGGB16, PIXFMT_BAYER_GRBG16, \
+    PIXFMT_BAYER_GBRG16, PIXFMT_BAYER_BGGR16 = range(16, 24)
+PIXFMT_BAYER_BYTES = {f: 1 if f < PIXFMT_BAYER_RGGB16 else 2 for f in range(16, 24)}
 
 
 class FrameGeometry(C.Structure):

@@ -414,14 +414,15 @@ struct Pipeline {
             throw std::runtime_error("Image format is not supported: null pixels or stride < width * bytes per pixel");
         }
         // the upload that takes the frame: SCALED and FORMAT carry format / bits / limited_range, COLOR carries the channels
-        enum { GRAY, COLOR, FORMAT, SCALED } how = in.geo ? SCALED : pf.bpp == 2 || pf.rgb || pf.limited ? FORMAT : pf.bpp != 1 ? COLOR : GRAY;
+        enum { GRAY, COLOR, FORMAT, SCALED } how = in.geo ? SCALED : pf.bpp == 2 || pf.rgb || pf.limited || pf.bayer ? FORMAT : pf.bpp != 1 ? COLOR : GRAY;
         const uint8_t *pixels = in.pixels;
         int stride = in.stride;
         if (how == SCALED ? !have_scaled_upload() : how == FORMAT ? !have_format_upload() : how == COLOR && !have_color_upload()) {
             if (how == SCALED && in.on_device) throw std::runtime_error("Image geometry is not supported: this library cannot scale a frame in device memory");
             gray_scratch.resize((size_t)cols * rows);
             if (how == SCALED)
-                scale_frame(gray_scratch.data(), cols, rows, crop_origin(pixels, stride, *in.geo, pf.bpp), stride, in.geo->crop_width, in.geo->crop_height, pf);
+                scale_frame(gray_scratch.data(), cols, rows, crop_origin(pixels, stride, *in.geo, pf.bpp), stride, in.geo->crop_width, in.geo->crop_height,
+                            crop_pixel_format(pf, *in.geo));
             else reduce_frame(gray_scratch.data(), pixels, stride, cols, rows, pf);   // BGR(A): cv::cvtColor BGR(A)2GRAY, (B*1868 + G*9617 + R*4899 + 8192) >> 14
             pixels = gray_scratch.data();
             stride = cols;

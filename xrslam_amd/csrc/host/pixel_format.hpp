@@ -7,11 +7,14 @@
 //                                                  GRAY16: mask ffff, shift bits - 8;  P010, UYVY: ffff, 8;  YUYV: 00ff, 0
 //   3 / 4   (BGR8, BGRA8, RGB8, RGBA8)             gray = (B*1868 + G*9617 + R*4899 + 8192) >> 14, byte 3 ignored
 //   limited range (not for the 3 / 4 byte formats) gray' = min(255, ((max(gray, 16) - 16) * 255 + 109) / 219)
+//   Bayer mosaics (BAYER_*8 / *16: 1 / 2 bytes)    the sample s is the 1 / 2-byte value above (GRAY16's rule for *16); the gray value
+//                                                  needs the pixel's neighbours: bayer_gray below, a whole frame at a time
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include "../../../include/xrslam_hip.h"
 
@@ -23,6 +26,8 @@ struct PixelFormat {
     uint32_t shift = 0;
     bool rgb = false;         // 3 / 4-byte formats: byte 0 is R
     bool limited = false;
+    bool bayer = false;       // a colour-filter mosaic of 1 / 2-byte samples: the gray value is bayer_gray's, not reduce_pixel's
+    int px = 0, py = 0;       // its pattern as a phase of RGGB: the colour site of (x, y) is RGGB's at ((x + px) & 1, (y + py) & 1)
 };
 
 // nullptr, or which argument is wrong and why (the callers put their own name in front)
@@ -41,9 +46,23 @@ inline const char *describe_pixel_format(int format, int bits, int limited_range
             break;
         case XRHIP_PIXFMT_YUYV: f.bpp = 2; f.mask = 0xffu; break;
         case XRHIP_PIXFMT_UYVY: case XRHIP_PIXFMT_P010: f.bpp = 2; f.shift = 8; break;
+        case XRHIP_PIXFMT_BAYER_RGGB8: case XRHIP_PIXFMT_BAYER_GRBG8: case XRHIP_PIXFMT_BAYER_GBRG8: case XRHIP_PIXFMT_BAYER_BGGR8:
+        case XRHIP_PIXFMT_BAYER_RGGB16: case XRHIP_PIXFMT_BAYER_GRBG16: case XRHIP_PIXFMT_BAYER_GBRG16: case XRHIP_PIXFMT_BAYER_BGGR16: {
+            const int pattern = (format - XRHIP_PIXFMT_BAYER_RGGB8) & 3;   // RGGB, GRBG, GBRG, BGGR = phase (0,0), (1,0), (0,1), (1,1)
+            f.bayer = true;
+            f.px = pattern & 1;
+            f.py = pattern >> 1;
+            if (format >= XRHIP_PIXFMT_BAYER_RGGB16) {   // the sample is reduced like GRAY16
+                if (bits != 0 && (bits < 8 || bits > 16)) return "bits must be 0 (= 16) or 8..16";
+                f.bpp = 2;
+                f.shift = (uint32_t)((bits ? bits : 16) - 8);
+            }
+            break;
+        }
         default: return "format is not one of XRHIP_PIXFMT_*";
     }
     if (limited_range && f.bpp >= 3) return "limited_range does not apply to the RGB / BGR formats";
+    if (limited_range && f.bayer) return "limited_range does not apply to the Bayer formats";
     f.limited = limited_range != 0;
     out = f;
     return nullptr;
@@ -62,9 +81,47 @@ inline uint8_t reduce_pixel(const uint8_t *p, const PixelFormat &f) {
     return f.limited ? expand_limited_range(g) : (uint8_t)g;
 }
 
+// ------------------------------------------------------------------------------------------------ Bayer mosaics
+// Bilinear demosaicing followed by the BGR weights, in exact integer arithmetic with one rounding (xrslam_hip.h has the definition;
+// the device kernel k_upload_bayer and the numpy model tests/bayer_model.py give the same bits).  The frame is n_x x n_y samples;
+// neighbours outside it mirror without repeating the edge (-1 -> 1, n -> n - 2), which keeps every neighbour on a site of the colour
+// it stands for; n_x, n_y >= 2.  Every sum is four times the bilinear estimate; the weights sum to 16384.
+inline int bayer_mirror(int i, int n) { return i < 0 ? -i : i >= n ? 2 * n - 2 - i : i; }
+inline uint8_t bayer_gray(const uint8_t *src, long long stride, int n_x, int n_y, int x, int y, const PixelFormat &f) {
+    const int xl = bayer_mirror(x - 1, n_x), xr = bayer_mirror(x + 1, n_x), yu = bayer_mirror(y - 1, n_y), yd = bayer_mirror(y + 1, n_y);
+    const auto s = [&](int xx, int yy) -> uint32_t { return reduce_pixel(src + (size_t)yy * (size_t)stride + (size_t)xx * f.bpp, f); };
+    const uint32_t C = 4 * s(x, y), Hh = 2 * (s(xl, y) + s(xr, y)), Vv = 2 * (s(x, yu) + s(x, yd)), P = (Hh + Vv) / 2;
+    const uint32_t X = s(xl, yu) + s(xr, yu) + s(xl, yd) + s(xr, yd);
+    const int cx = (x + f.px) & 1, cy = (y + f.py) & 1;   // RGGB's site: (0,0) red, (1,1) blue, (1,0) green between reds, (0,1) between blues
+    uint32_t R4, G4, B4;
+    if (cx == cy) {
+        G4 = P;
+        R4 = cx ? X : C;
+        B4 = cx ? C : X;
+    } else {
+        G4 = C;
+        R4 = cy ? Vv : Hh;
+        B4 = cy ? Hh : Vv;
+    }
+    return (uint8_t)((4899u * R4 + 9617u * G4 + 1868u * B4 + 32768u) >> 16);
+}
+// The format of the crop of `g` taken as a Bayer frame of its own: the pattern phase shifts with the crop's origin
+inline PixelFormat crop_pixel_format(PixelFormat f, const xrhip_frame_geometry &g) {
+    if (f.bayer) {
+        f.px ^= g.crop_x & 1;
+        f.py ^= g.crop_y & 1;
+    }
+    return f;
+}
+
 // `rows` rows of `cols` pixels at `src` (rows `stride` bytes apart, any alignment) into the dense gray plane `dst`: reads
 // cols * f.bpp bytes of each of the rows and nothing else
 inline void reduce_frame(uint8_t *dst, const uint8_t *src, int stride, int cols, int rows, const PixelFormat &f) {
+    if (f.bayer) {
+        for (int y = 0; y < rows; ++y)
+            for (int x = 0; x < cols; ++x) dst[(size_t)y * cols + x] = bayer_gray(src, stride, cols, rows, x, y, f);
+        return;
+    }
     for (int y = 0; y < rows; ++y) {
         const uint8_t *s = src + (size_t)y * stride;
         uint8_t *d = dst + (size_t)y * cols;
@@ -107,8 +164,14 @@ inline const uint8_t *crop_origin(const uint8_t *pixels, long long stride, const
 }
 
 // `src`: the crop's first byte (rows `stride` bytes apart, cw x ch pixels of f.bpp bytes) -> the dense W x H plane `dst`.  Reads the
-// cw * f.bpp bytes of each of the ch rows and nothing else.
+// cw * f.bpp bytes of each of the ch rows and nothing else.  A Bayer crop (f: crop_pixel_format) is a Bayer frame of its own: it is
+// demosaiced whole, its neighbours mirrored at the crop's edges, and the gray crop is scaled.
 inline void scale_frame(uint8_t *dst, int W, int H, const uint8_t *src, long long stride, int cw, int ch, const PixelFormat &f) {
+    if (f.bayer) {
+        std::vector<uint8_t> gray((size_t)cw * ch);
+        reduce_frame(gray.data(), src, (int)stride, cw, ch, f);
+        return scale_frame(dst, W, H, gray.data(), cw, cw, ch, PixelFormat());
+    }
     const uint32_t area = (uint32_t)cw * (uint32_t)ch, half = area / 2;
     for (int Y = 0; Y < H; ++Y) {
         const long long y0 = (long long)Y * ch, y1 = y0 + ch;

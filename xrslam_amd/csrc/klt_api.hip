@@ -135,9 +135,13 @@ struct xrhip_klt {
     double view_ms = 0;
     long long view_n = 0;
     // frames larger than the plane (xrhip_image_upload_scaled): the crop of a host frame in HBM, where k_upload_scaled reads it.
-    // Nothing of it exists before the first scaled upload of a host frame.
+    // Nothing of it exists before the first scaled (or Bayer) upload of a host frame.
     uint8_t *scale_src = nullptr;
     size_t scale_cap = 0;
+    // Bayer mosaics (XRHIP_PIXFMT_BAYER_*): a host mosaic is staged in scale_src as well (k_upload_bayer reads it there); a scaled one
+    // is demosaiced into this cw x ch gray scratch, which k_upload_scaled then reads.  Allocated by the first scaled Bayer frame.
+    uint8_t *bayer_gray = nullptr;
+    size_t bayer_gray_cap = 0;
     hipEvent_t span_t0 = nullptr, span_t1 = nullptr;   // xrhip_debug_stream_span
     // LK parameters (xrhip_klt_set_lk_params): at the reference's values, with the switch off, the specialised kernels run
     xrhip_lk_params lk{XRHIP_KLT_WIN, XRHIP_KLT_LEVELS - 1, 30, 0.01};
@@ -581,6 +585,7 @@ void xrhip_klt_destroy(xrhip_klt *c) {
     if (c->view_t0) hipEventDestroy(c->view_t0);
     if (c->view_t1) hipEventDestroy(c->view_t1);
     hipFree(c->scale_src);
+    hipFree(c->bayer_gray);
     if (c->span_t0) hipEventDestroy(c->span_t0);
     if (c->span_t1) hipEventDestroy(c->span_t1);
     for (int i = 0; i < xrhip_klt::UP_SLOTS; ++i) {
@@ -821,6 +826,37 @@ static int upload_into(xrhip_klt *c, const FrameSource &s, uint8_t *dst) {
     return slot_in_flight(c, slot);
 }
 
+// An HBM scratch of the context grown to `bytes` (whatever the context has issued may still be reading the old one)
+static int grow_scratch(xrhip_klt *c, uint8_t *&buf, size_t &cap, size_t bytes) {
+    if (bytes <= cap) return XRHIP_OK;
+    const int rc = wait_before_growth(c);
+    if (rc) return rc;
+    hipFree(buf);
+    buf = nullptr;
+    cap = 0;
+    XR_HIP(hipMalloc(&buf, bytes));
+    cap = bytes;
+    return XRHIP_OK;
+}
+// k_upload_scaled's arguments: the cw x ch crop at `src` (bpp, fmt: as UploadArgs) down to the context's plane at `dst`
+static ScaleArgs scale_args(const xrhip_klt *c, const uint8_t *src, int stride, int bpp, int fmt, int cw, int ch, uint8_t *dst) {
+    ScaleArgs a{};
+    a.src = src;
+    a.sstride = stride;
+    a.dst = dst;
+    a.w = c->w;
+    a.h = c->h;
+    a.bpp = bpp;
+    a.fmt = fmt;
+    a.cw = cw;
+    a.ch = ch;
+    a.wide = ((uint64_t)c->w * (uint64_t)cw >> 32) != 0 || ((uint64_t)c->h * (uint64_t)ch >> 32) != 0;
+    return a;
+}
+static dim3 grid_of_fours(size_t pixels) {   // a lane owns four plane pixels, a block 1024; grid-stride beyond 2048 blocks
+    const unsigned n4 = (unsigned)((pixels + 3) / 4);
+    return dim3(std::max(1u, std::min((n4 + 255u) / 256u, 2048u)));
+}
 // The crop of a frame of any pixel format, area-averaged down to the context's plane (k_upload_scaled) on the way in.  A frame in HBM
 // is read where it lies.  A host frame: only the crop is staged (rows of cw * bpp bytes, packed) through the pinned slots, which grow
 // as they do for colour; the slot is then copied to an HBM scratch and the kernel reads that.  Neighbouring plane pixels share
@@ -831,33 +867,14 @@ static int upload_into(xrhip_klt *c, const FrameSource &s, uint8_t *dst) {
 // member: on the group's front-end queue, behind a pending upload, which is submitted first).
 static int upload_scaled_into(xrhip_klt *c, const FrameSource &s, uint8_t *dst) {
     const int cw = s.geo->crop_width, ch = s.geo->crop_height;
-    ScaleArgs a{};
-    a.src = xrh::crop_origin(s.pixels, s.stride, *s.geo, s.pf.bpp);
-    a.sstride = s.stride;
-    a.dst = dst;
-    a.w = c->w;
-    a.h = c->h;
-    a.bpp = s.pf.bpp;
-    a.fmt = upf_word(s.pf);
-    a.cw = cw;
-    a.ch = ch;
-    a.wide = ((uint64_t)c->w * (uint64_t)cw >> 32) != 0 || ((uint64_t)c->h * (uint64_t)ch >> 32) != 0;
-    const unsigned n4 = (unsigned)(((size_t)c->w * c->h + 3) / 4);
-    const dim3 grid(std::max(1u, std::min((n4 + 255u) / 256u, 2048u)));
+    ScaleArgs a = scale_args(c, xrh::crop_origin(s.pixels, s.stride, *s.geo, s.pf.bpp), s.stride, s.pf.bpp, upf_word(s.pf), cw, ch, dst);
+    const dim3 grid = grid_of_fours((size_t)c->w * c->h);
     const size_t row = (size_t)cw * s.pf.bpp, bytes = row * ch;
     const uint8_t *staged = nullptr;   // host frame: the slot that holds the crop
     int slot = 0;
     if (!s.on_device) {
-        int rc = XRHIP_OK;
-        if (bytes > c->scale_cap) {
-            rc = wait_before_growth(c);
-            if (rc) return rc;
-            hipFree(c->scale_src);
-            c->scale_src = nullptr;
-            c->scale_cap = 0;
-            XR_HIP(hipMalloc(&c->scale_src, bytes));
-            c->scale_cap = bytes;
-        }
+        int rc = grow_scratch(c, c->scale_src, c->scale_cap, bytes);
+        if (rc) return rc;
         rc = slot_fill(c, a.src, s.stride, row, ch, slot);
         if (rc) return rc;
         staged = c->up_buf[slot];
@@ -874,6 +891,59 @@ static int upload_scaled_into(xrhip_klt *c, const FrameSource &s, uint8_t *dst) 
     return slot_in_flight(c, slot);
 }
 
+// A Bayer mosaic (XRHIP_PIXFMT_BAYER_*), demosaiced to gray by k_upload_bayer: a launch of its own in the context's order, like the
+// scaled upload and for its reason -- every row of the mosaic is read by the lanes of three plane rows, so a host frame goes through
+// the pinned slot to the HBM scratch (scale_src) and the kernel reads that; a mosaic in HBM is read where it lies.  Not part of the
+// shared upload launch (a group member: on the group's front-end queue, behind a pending upload, which is submitted first).
+// Scaled: the crop is a Bayer frame of its own (its phase shifted by the crop's origin, neighbours mirrored at its edges: only the
+// crop's bytes are read); it is demosaiced into the cw x ch gray scratch, from which k_upload_scaled takes it as a gray crop.
+static int upload_bayer_into(xrhip_klt *c, const FrameSource &s, uint8_t *dst) {
+    const xrh::PixelFormat pf = s.scaled ? xrh::crop_pixel_format(s.pf, *s.geo) : s.pf;
+    BayerArgs a{};
+    a.src = s.scaled ? xrh::crop_origin(s.pixels, s.stride, *s.geo, pf.bpp) : s.pixels;
+    a.sstride = s.stride;
+    a.dst = dst;
+    a.w = s.scaled ? s.geo->crop_width : c->w;
+    a.h = s.scaled ? s.geo->crop_height : c->h;
+    a.bpp = pf.bpp;
+    a.shift = (int)pf.shift;
+    a.px = pf.px;
+    a.py = pf.py;
+    const size_t pixels = (size_t)a.w * a.h, row = (size_t)a.w * pf.bpp, bytes = row * a.h;
+    int rc = XRHIP_OK;
+    if (s.scaled) {
+        rc = grow_scratch(c, c->bayer_gray, c->bayer_gray_cap, pixels);
+        if (rc) return rc;
+        a.dst = c->bayer_gray;
+    }
+    const ScaleArgs sa = scale_args(c, c->bayer_gray, a.w, 1, 0, a.w, a.h, dst);   // (scaled only)
+    const bool scaled = s.scaled;
+    const dim3 grid = grid_of_fours(pixels), scale_grid = grid_of_fours((size_t)c->w * c->h);
+    const uint8_t *staged = nullptr;   // host frame: the slot that holds the mosaic
+    int slot = 0;
+    if (!s.on_device) {
+        rc = grow_scratch(c, c->scale_src, c->scale_cap, bytes);
+        if (rc) return rc;
+        rc = slot_fill(c, a.src, s.stride, row, a.h, slot);
+        if (rc) return rc;
+        staged = c->up_buf[slot];
+        a.src = c->scale_src;
+        a.sstride = (int)row;
+    }
+    rc = klt_run(c, [=](hipStream_t st) {
+        if (staged) XR_HIP(hipMemcpyAsync(c->scale_src, staged, bytes, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_upload_bayer, grid, dim3(256), 0, st, a);
+        XR_HIP(hipGetLastError());
+        if (scaled) {
+            hipLaunchKernelGGL(k_upload_scaled, scale_grid, dim3(256), 0, st, sa);
+            XR_HIP(hipGetLastError());
+        }
+        return XRHIP_OK;
+    });
+    if (rc || !staged) return rc;
+    return slot_in_flight(c, slot);
+}
+
 // Every xrhip_image_upload* entry point (`who`).  distorted: the frame is as the camera recorded it and k_undistort rectifies it into
 // the plane -- reduced / scaled into undist_src first, rectified second: the gray frame takes the place of the one a gray camera of
 // the plane's size would have recorded; such a frame already in HBM is remapped where it lies.
@@ -884,13 +954,13 @@ static int upload_frame(xrhip_image *im, const FrameSource &s, const char *bad_f
     if (distorted && !c->have_undist) return frame_fail(XRHIP_ESTATE, who, "no undistortion map (xrhip_klt_set_undistort_map)");
     const uint8_t *remap_src = c->undist_src;
     int remap_stride = c->w;
-    if (distorted && s.on_device && !s.scaled && s.pf.bpp == 1 && upf_word(s.pf) == 0) {
+    if (distorted && s.on_device && !s.scaled && !s.pf.bayer && s.pf.bpp == 1 && upf_word(s.pf) == 0) {
         remap_src = s.pixels;
         remap_stride = s.stride;
     } else {
         // (a host buffer may be reused by the caller as soon as we return: PushImage deep-copies, the pinned slot holds our copy)
         uint8_t *dst = distorted ? c->undist_src : im->raw;
-        rc = s.scaled ? upload_scaled_into(c, s, dst) : upload_into(c, s, dst);
+        rc = s.pf.bayer ? upload_bayer_into(c, s, dst) : s.scaled ? upload_scaled_into(c, s, dst) : upload_into(c, s, dst);
         if (rc) return rc;
     }
     if (distorted) {   // (not batched: a remap per frame on a path the bench's resident / rectified inputs do not take)

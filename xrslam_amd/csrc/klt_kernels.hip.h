@@ -1665,6 +1665,102 @@ __global__ __launch_bounds__(256) void k_upload_scaled(ScaleArgs a) {
     d_upload_scaled<1>(a);
 }
 
+// ----------------------------------------------------------------------------------------------------- Bayer mosaics (XRHIP_PIXFMT_BAYER_*)
+// A raw colour-filter mosaic of w x h samples (bpp 1: a byte; bpp 2: little endian, s = min(255, v >> shift) as GRAY16) demosaiced to
+// the dense w x h gray plane: bilinear demosaicing and the BGR weights in exact integers with one rounding (xrslam_hip.h has the
+// definition, host/pixel_format.hpp: bayer_gray the same arithmetic).  (px, py): the pattern as a phase of RGGB -- the colour site of
+// (x, y) is RGGB's at ((x + px) & 1, (y + py) & 1).  Neighbours outside the frame mirror without repeating the edge.
+struct BayerArgs {
+    const uint8_t *src;
+    int sstride;
+    uint8_t *dst;   // dense w x h
+    int w, h;       // >= 2
+    int bpp, shift;
+    int px, py;
+};
+// gray of a pixel from its sample c, the sums of its horizontal (hs), vertical (vs) and diagonal (ds) neighbours and its RGGB site
+__device__ __forceinline__ uint32_t bayer_weigh(uint32_t c, uint32_t hs, uint32_t vs, uint32_t ds, int cx, int cy) {
+    uint32_t r4, g4, b4;
+    if (cx == cy) {   // red (0,0) / blue (1,1)
+        g4 = hs + vs;
+        r4 = cx ? ds : 4u * c;
+        b4 = cx ? 4u * c : ds;
+    } else {          // green between reds (1,0) / between blues (0,1) in its row
+        g4 = 4u * c;
+        r4 = 2u * (cy ? vs : hs);
+        b4 = 2u * (cy ? hs : vs);
+    }
+    return (4899u * r4 + 9617u * g4 + 1868u * b4 + 32768u) >> 16;
+}
+__device__ __forceinline__ int bayer_mirror(int i, int n) { return i < 0 ? -i : i >= n ? 2 * n - 2 - i : i; }
+// one pixel, byte by byte, neighbours mirrored
+template <int BPP> __device__ __forceinline__ uint32_t bayer_gray1(const BayerArgs &a, int x, int y) {
+    const int xs[3] = {bayer_mirror(x - 1, a.w), x, bayer_mirror(x + 1, a.w)};
+    uint32_t s[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const uint8_t *row = a.src + (size_t)(r == 1 ? y : bayer_mirror(y + r - 1, a.h)) * (size_t)a.sstride;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const uint8_t *p = row + (size_t)xs[k] * BPP;
+            s[r][k] = BPP == 2 ? min(255u, ((uint32_t)p[0] | ((uint32_t)p[BPP - 1] << 8)) >> (uint32_t)a.shift) : (uint32_t)p[0];
+        }
+    }
+    return bayer_weigh(s[1][1], s[1][0] + s[1][2], s[0][1] + s[2][1], s[0][0] + s[0][2] + s[2][0] + s[2][2], (x + a.px) & 1, (y + a.py) & 1);
+}
+// A lane owns four consecutive plane pixels = one dword store, as in d_upload_reduce.  Where the four and their neighbours lie inside
+// the frame (columns x - 1 .. x + 4 of rows y - 1 .. y + 1) it fetches, per row, the aligned dwords that cover those six samples:
+// BPP 2: the 12 bytes are three dwords' worth; BPP 1: two overlapping dwords' worth, columns x - 1 .. x + 2 and x + 1 .. x + 4 -- either
+// way every fetched dword holds one of the six samples' bytes, so nothing outside the frame's pages is touched.  Each row is read by
+// the lanes of three plane rows: the repeats are served by the caches (a host frame is staged in HBM first: klt_api.hip).  Lanes at
+// the first or last column or row, groups that straddle a row end (w % 4 != 0) and the plane's tail go byte by byte.
+template <int BPP> __device__ __forceinline__ void d_upload_bayer(const BayerArgs &a) {
+    const uint32_t w = (uint32_t)a.w, h = (uint32_t)a.h, total = w * h;
+    const uint32_t n4 = (total + 3u) >> 2;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n4; i += gridDim.x * 256u) {
+        const uint32_t p0 = i << 2;
+        const uint32_t y = p0 / w, x = p0 - y * w;
+        if (x >= 1u && x + 5u <= w && y >= 1u && y + 1u < h) {   // (the four lie in one row and p0 + 4 <= total follows)
+            uint32_t s[3][6];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const uintptr_t ad = reinterpret_cast<uintptr_t>(a.src + (size_t)(y + r - 1) * (size_t)a.sstride + (size_t)(x - 1u) * BPP);
+                if (BPP == 2) {
+                    uint32_t d[4];
+                    load_dwords_unaligned<3>(ad, d);
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) s[r][k] = min(255u, ((d[k >> 1] >> (16 * (k & 1))) & 0xffffu) >> (uint32_t)a.shift);
+                } else {
+                    uint32_t lo[2], hi[2];
+                    load_dwords_unaligned<1>(ad, lo);
+                    load_dwords_unaligned<1>(ad + 2, hi);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s[r][k] = (lo[0] >> (8 * k)) & 255u;
+                    s[r][4] = (hi[0] >> 16) & 255u;
+                    s[r][5] = hi[0] >> 24;
+                }
+            }
+            const int cy = (int)(y + (uint32_t)a.py) & 1;
+            uint32_t g[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                g[k] = bayer_weigh(s[1][k + 1], s[1][k] + s[1][k + 2], s[0][k + 1] + s[2][k + 1], s[0][k] + s[0][k + 2] + s[2][k] + s[2][k + 2],
+                                   (int)(x + (uint32_t)k + (uint32_t)a.px) & 1, cy);
+            reinterpret_cast<uint32_t *>(a.dst)[i] = g[0] | (g[1] << 8) | (g[2] << 16) | (g[3] << 24);
+        } else {
+            const uint32_t pe = p0 + 4u < total ? p0 + 4u : total;
+            for (uint32_t p = p0; p < pe; ++p) {
+                const uint32_t py = p / w;
+                a.dst[p] = (uint8_t)bayer_gray1<BPP>(a, (int)(p - py * w), (int)py);
+            }
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_upload_bayer(BayerArgs a) {
+    if (a.bpp == 2) return d_upload_bayer<2>(a);
+    d_upload_bayer<1>(a);
+}
+
 // ---------------------------------------------------------------------------------------------- tracking view (xrhip_image_render_view)
 // Line segments and discs over a frame's gray plane, all in integers.  Which primitive a pixel shows must not depend on how the GPU
 // schedules the lanes: k_view_stamp takes atomicMax of a word ordered like the priority rule into a 32-bit owner plane (cleared per

@@ -7,13 +7,14 @@
 //
 //   xrslam-player --slam configs/euroc_slam.yaml --device configs/euroc_sensor.yaml --euroc <dir>/mav0
 //                 [--out traj.tum] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined]
-//                 [--push-color] [--push-format gray16|rgb|rgba] [--push-scaled] [--cov-out FILE]
+//                 [--push-color] [--push-format gray16|rgb|rgba|bayer_rggb8|bayer_bggr16] [--push-scaled] [--cov-out FILE]
 //
 // (--push-color: a colour PNG is pushed as BGR / BGRA with channel 3 / 4 and reduced to gray by the library instead of by the reader.)
 // (--push-scaled: a PNG larger than cam0.resolution is pushed at its own size, the whole frame as the crop, and cropped / area-scaled
 // down by the library -- through any --push-color / --push-format setting; without the flag a size mismatch is an error.)
 // (--push-format: a 16-bit PNG is handed to the library as GRAY16 instead of being stripped to its high byte by the reader; a colour
-// PNG as RGB8 / RGBA8 -- XRSLAMAmdPushImageFormat.)
+// PNG as RGB8 / RGBA8 -- XRSLAMAmdPushImageFormat.  bayer_rggb8 / bayer_bggr16: the gray PNG becomes a raw mosaic whose every site
+// holds the gray value -- bytes, or 16-bit samples with the value in the high byte -- and is pushed as BAYER_RGGB8 / BAYER_BGGR16.)
 // (--pipelined: XRSLAMAmdSetThreading(1), the reference's XRSLAM_ENABLE_THREADING build with deterministic hand-offs.)
 // The reference player's own command line (main.cpp:57-79) is accepted as well, so its invocations carry over:
 //
@@ -40,6 +41,7 @@
 #include "XRSLAM.h"
 #include "euroc_io.hpp"
 #include "../host/config.hpp"
+#include "../host/pixel_format.hpp"
 
 using namespace xrplayer;
 
@@ -60,6 +62,7 @@ int main(int argc, char **argv) {
     std::map<std::string, std::string> opt;
     bool undistort = true, host_undistort = false, pipelined = false, push_color = false, push_scaled = false;
     int png_keep = PNG_GRAY;   // --push-format
+    int push_bayer = -1;       // --push-format bayer_*: the XRSLAMAmdPixelFormat the gray frames are pushed as
     // the reference's option names (main.cpp:57-71) map onto ours
     const std::map<std::string, std::string> alias = {{"-sc", "slam"}, {"--slamconfig", "slam"}, {"-dc", "device"},
                                                       {"--deviceconfig", "device"}, {"-lc", "license"}, {"--license", "license"},
@@ -76,8 +79,10 @@ int main(int argc, char **argv) {
             if (f == "gray16") png_keep = PNG_KEEP_GRAY16;
             else if (f == "rgb") png_keep = PNG_KEEP_RGB;
             else if (f == "rgba") png_keep = PNG_KEEP_RGBA;
+            else if (f == "bayer_rggb8") push_bayer = XRSLAM_AMD_PIXEL_BAYER_RGGB8;
+            else if (f == "bayer_bggr16") push_bayer = XRSLAM_AMD_PIXEL_BAYER_BGGR16;
             else {
-                std::fprintf(stderr, "--push-format: gray16, rgb or rgba\n");
+                std::fprintf(stderr, "--push-format: gray16, rgb, rgba, bayer_rggb8 or bayer_bggr16\n");
                 return 2;
             }
         }
@@ -102,7 +107,7 @@ int main(int argc, char **argv) {
     }
     if (!opt.count("slam") || !opt.count("device") || !opt.count("euroc")) {
         std::fprintf(stderr, "usage: xrslam-player --slam cfg.yaml --device sensor.yaml --euroc <dir>/mav0 [--out traj.tum] "
-                             "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color] [--push-format gray16|rgb|rgba] [--push-scaled]\n"
+                             "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color] [--push-format gray16|rgb|rgba|bayer_rggb8|bayer_bggr16] [--push-scaled]\n"
                              "       [--cov-out FILE] [--view-out DIR [--view-every N] [--view-mode reference|age] [--view-trail K]]\n"
                              "   or: xrslam-player -sc cfg.yaml -dc sensor.yaml [--tum traj.tum] [--csv traj.csv] [-p] "
                              "euroc://<dir>/mav0 | tum://<dir>/mav0\n");
@@ -227,6 +232,15 @@ int main(int argc, char **argv) {
                 std::fprintf(stderr, "%s: %s\n", cam[ev.index].filename.c_str(), e.what());
                 break;
             }
+            if (push_bayer >= 0 && img.channels == 1 && img.pixel_format < 0) {   // the mosaic: every site gets the gray value
+                if (push_bayer >= XRSLAM_AMD_PIXEL_BAYER_RGGB16) {
+                    std::vector<uint8_t> m(img.px.size() * 2, 0);
+                    for (size_t i = 0; i < img.px.size(); ++i) m[2 * i + 1] = img.px[i];
+                    img.px.swap(m);
+                    img.channels = 2;
+                }
+                img.pixel_format = push_bayer;
+            }
             // the library copies cam0.resolution rows x columns out of the buffer it is handed
             // (XRSLAMManager.cpp:113-131 does the same with the configured size): a frame of any other size is an error
             const bool oversized = push_scaled && img.w >= (int)cfg.cam_resolution[0] && img.h >= (int)cfg.cam_resolution[1] &&
@@ -249,9 +263,13 @@ int main(int argc, char **argv) {
                 break;
             }
             const bool rectify_here = !oversized && undistort && cfg.cam_distortion_flag && !device_undistort;
-            if (img.channels != 1 && rectify_here) {   // the host remap takes gray: reduced first, rectified second, as in the library
+            const bool mosaic = img.pixel_format >= XRSLAM_AMD_PIXEL_BAYER_RGGB8;
+            if ((img.channels != 1 || mosaic) && rectify_here) {   // the host remap takes gray: reduced first, rectified second, as in the library
                 std::vector<uint8_t> g((size_t)img.w * img.h);
-                for (size_t i = 0; i < g.size(); ++i) {
+                xrh::PixelFormat pf;
+                if (mosaic && !xrh::describe_pixel_format(img.pixel_format, 0, 0, pf))
+                    xrh::reduce_frame(g.data(), img.px.data(), img.w * img.channels, img.w, img.h, pf);
+                for (size_t i = 0; i < g.size() && !mosaic; ++i) {
                     const uint8_t *c = &img.px[i * img.channels];
                     if (img.pixel_format == XRSLAM_AMD_PIXEL_GRAY16) g[i] = c[1];   // 16 significant bits: the high byte
                     else if (img.pixel_format >= 0) g[i] = (uint8_t)((c[0] * 4899 + c[1] * 9617 + c[2] * 1868 + 8192) >> 14);   // RGB(A)

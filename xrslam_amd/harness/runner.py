@@ -70,10 +70,12 @@ class XRSLAMAmdFrameFormat(C.Structure):
 # XRSLAMAmdPixelFormat (include/XRSLAM.h)
 PIXEL_FORMATS = {name: i for i, name in enumerate(("gray8", "bgr8", "bgra8", "rgb8", "rgba8", "gray16", "yuyv", "uyvy", "nv12", "i420",
                                                    "p010"))}
+PIXEL_FORMATS.update({name: 16 + i for i, name in enumerate(("bayer_rggb8", "bayer_grbg8", "bayer_gbrg8", "bayer_bggr8", "bayer_rggb16",
+                                                             "bayer_grbg16", "bayer_gbrg16", "bayer_bggr16"))})   # (11..15 are not formats)
 
 
 def frame_format(pixel_format):
-    """'yuyv', ('gray16', 10), ('nv12', 0, 1) or numbers in their place -> XRSLAMAmdFrameFormat (format, bits, limited_range)"""
+    """'yuyv', ('gray16', 10), ('nv12', 0, 1), 'bayer_grbg8', ('bayer_rggb16', 12) or numbers in their place -> XRSLAMAmdFrameFormat (format, bits, limited_range)"""
     if isinstance(pixel_format, XRSLAMAmdFrameFormat):
         return pixel_format
     f = tuple(pixel_format) if isinstance(pixel_format, (tuple, list)) else (pixel_format,)
