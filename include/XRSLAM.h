@@ -329,6 +329,25 @@ const char *XRSLAMAmdLastError(void);
  * results and by the statistics getters). */
 void XRSLAMAmdSetThreading(int mode);
 void XRSLAMAmdFlush(void);
+/* Masks: where in the frame the tracker must not look -- the vehicle's hood, a controller, a timestamp overlay, the black corners of
+ * a rectified fisheye frame, what a segmentation network on the same GPU has just labelled (cv::goodFeaturesToTrack's mask, OpenVINS
+ * use_mask, VINS fisheye_mask).  A mask is a W x H plane of bytes at the working resolution (cam0.resolution) and describes the
+ * image the tracker works on, after format reduction, crop / scale and device undistortion: a byte != 0 may be used (1, 128 and 255
+ * are the same), 0 is excluded.  Host memory or HBM (on_device), any base alignment, any stride >= W.
+ *   XRSLAMAmdSetMask           the static mask: stays until cleared (mask == NULL)
+ *   XRSLAMAmdSetNextFrameMask  the mask of the NEXT camera frame pushed through any of the push entry points; that frame consumes
+ *                              it (a frame that is dropped, e.g. for a bad format, takes its mask with it); NULL withdraws it
+ * The effective mask of a frame is static != 0 && per_frame != 0, a missing one counting as all ones; with neither, everything runs
+ * exactly as it does without masks.  No new key point is detected on an excluded pixel -- and the corner threshold is taken over the
+ * visible pixels only, so hiding the strongest corner lowers it -- and a tracked key point whose new position rounds to an excluded
+ * pixel is dropped like one that failed the tracker's own gates (include/xrslam_hip.h, "Masks", has the rules).
+ * A host mask is copied during the call.  A static HBM mask has been read on return; a per-frame HBM mask must stay valid until the
+ * frame has been pushed.  Works in both threading modes: the mask is bound to the frame when it is pushed.
+ * Returns 1 on success; 0 with the reason in XRSLAMAmdLastError for stride < W, no instance, or an instance that is a member of a
+ * group -- the mask in force (or none) then stays as it was.  A masked instance cannot join a group (XRSLAMAmdInstanceJoinGroup fails).
+ * Not here: masks at the source geometry of a scaled frame or in the distorted image, a configuration key, the CPU-reference pipeline. */
+int XRSLAMAmdSetMask(const void *mask, int stride, int on_device);
+int XRSLAMAmdSetNextFrameMask(const void *mask, int stride, int on_device);
 
 /* ---- tracking view (additive) ----
  * XRSLAM_RESULT_FEATURES fills XRSLAMFeatures::pos with the pixel positions of the key points of the newest tracked frame that have a
@@ -407,6 +426,8 @@ int XRSLAMAmdInstanceGetTrackerParams(XRSLAMAmdInstance *inst, XRSLAMAmdTrackerP
 void XRSLAMAmdInstanceGetInitReport(XRSLAMAmdInstance *inst, XRSLAMAmdInitReport *out);
 const char *XRSLAMAmdInstanceLastError(XRSLAMAmdInstance *inst);
 void XRSLAMAmdInstanceSetThreading(XRSLAMAmdInstance *inst, int mode);
+int XRSLAMAmdInstanceSetMask(XRSLAMAmdInstance *inst, const void *mask, int stride, int on_device);
+int XRSLAMAmdInstanceSetNextFrameMask(XRSLAMAmdInstance *inst, const void *mask, int stride, int on_device);
 void XRSLAMAmdInstanceFlush(XRSLAMAmdInstance *inst);
 int XRSLAMAmdInstanceGetFeatures(XRSLAMAmdInstance *inst, XRSLAMAmdFeature *out, int cap, double *timestamp);
 void XRSLAMAmdInstanceSetFeatureHistory(XRSLAMAmdInstance *inst, int frames);

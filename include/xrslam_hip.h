@@ -187,6 +187,36 @@ int xrhip_image_upload_scaled_distorted(xrhip_image *img, const void *pixels, in
 int xrhip_debug_stream_span(xrhip_klt *ctx, int phase, double *ms);
 /* parity aid: the 8-bit frame xrhip_image_preprocess will read */
 int xrhip_debug_get_raw(xrhip_image *img, uint8_t *out);
+/* Masks: where in the frame not to look (cv::goodFeaturesToTrack's mask; the hood, a controller, a fisheye frame's black corners,
+ * what a segmentation network on the same device has just labelled).  A mask is a width x height plane of bytes at the context's
+ * resolution and describes the image the tracker works on (after format reduction, crop / scale and device undistortion): a byte
+ * != 0 means the pixel may be used (1, 128 and 255 are the same), 0 excludes it.  Two sources, combined with AND:
+ *   static     xrhip_klt_set_mask: belongs to the context, stays until cleared (mask == NULL)
+ *   per frame  xrhip_image_set_mask: belongs to the frame the image holds -- valid after its upload and before preprocess / detect /
+ *              track use the image; NULL clears it; the next upload into the image drops it
+ * effective = static != 0 && per_frame != 0, a missing source counting as all ones.  With neither the image has no mask and every call
+ * does what it did before there were masks: the same kernels, the same arguments, nothing more allocated, launched or copied.
+ * The effective mask of a frame is decided by the first of xrhip_image_set_mask / preprocess / detect / track after the upload (one
+ * launch, k_mask_ingest, in the context's order); a static mask set later applies to later frames.
+ * Detection (xrhip_image_detect, also behind xrhip_image_prefetch_detect) is cv::goodFeaturesToTrack(image, ..., mask):
+ *   - the Harris response plane is that of the whole image, unchanged;
+ *   - the quality threshold is 1e-3 * max over the pixels whose effective mask is nonzero: hiding the strongest corner lowers it;
+ *   - non-maximum suppression compares all eight neighbours, masked or not (cv::dilate of the whole plane);
+ *   - a pixel is a candidate only if its own mask byte is nonzero; everything behind the candidate list (visiting order, 20-pixel
+ *     spacing, Poisson-disk filter against the existing points, 20-pixel border) is unchanged.
+ *   An all-zero effective mask: no new key points, no error.
+ * Tracking (xrhip_image_track, cur -> next): the reference's gates run unchanged and first; a point that passes them at (x, y) is
+ * then dropped (status 0, position not written) if the effective mask of `next` is zero at pixel (floor(x + 0.5), floor(y + 0.5)).
+ * The gate runs on the device (the mask may exist nowhere but in HBM).  cur's mask plays no part; xrhip_image_lk ignores masks.
+ * `mask`: a host pointer (copied during the call), or an HBM pointer when on_device (any base alignment, any stride_bytes >= width;
+ * xrhip_klt_set_mask has read it on return, xrhip_image_set_mask reads it in the context's stream order, like an uploaded frame).
+ * XRHIP_EINVAL: stride_bytes < width, a null context / image -- the previous mask (or none) stays in force.  XRHIP_ESTATE: the context
+ * is a member of a group (whose shared launches are the unmasked kernels), or the image holds no frame.  A context with a static
+ * mask, or one whose images have been handed a per-frame mask, cannot join a group (xrhip_klt_join_group: XRHIP_ESTATE).
+ * xrhip_debug_get_mask (parity aid): the effective plane, width * height bytes of 0 / 1; XRHIP_ESTATE if the image has none. */
+int xrhip_klt_set_mask(xrhip_klt *ctx, const void *mask, int stride_bytes, int on_device);
+int xrhip_image_set_mask(xrhip_image *img, const void *mask, int stride_bytes, int on_device);
+int xrhip_debug_get_mask(xrhip_image *img, uint8_t *out);
 /* Development / parity aids of the pyramid build (xrhip_image_preprocess): on = 1 (default) builds the CLAHE plane, the three
    pyrDown levels and all Scharr planes in one launch, 0 in the five launches it replaces (same bits: tests/test_klt_gpu.py);
    get_level_padded returns a level's image plane including its 21-pixel reflect-101 border (out may be NULL: sizes only). */

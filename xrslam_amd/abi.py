@@ -190,3 +190,15 @@ class FrameGeometry(C.Structure):
     """xrhip_frame_geometry = XRSLAMAmdFrameGeometry: the crop of a src_width x src_height frame that becomes the working image"""
     _fields_ = [("src_width", C.c_int), ("src_height", C.c_int), ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int),
                 ("crop_height", C.c_int)]
+
+
+def mask_args(mask, w, h, on_device=False, stride=None):
+    """-> (pointer, row stride in bytes) of a w x h byte mask for xrhip_klt_set_mask / xrhip_image_set_mask / XRSLAMAmdSetMask /
+    XRSLAMAmdSetNextFrameMask: None (clears), a uint8 array [h][w] whose rows may be strided (the caller keeps it alive for the call), or
+    -- on_device -- a device pointer (int) with its row stride.  `stride` overrides the array's own."""
+    if mask is None:
+        return None, 0
+    if on_device:
+        return C.c_void_p(int(mask)), int(stride)
+    assert mask.dtype == np.uint8 and mask.shape == (h, w) and mask.strides[1] == 1, (mask.dtype, mask.shape, mask.strides)
+    return C.c_void_p(mask.ctypes.data), mask.strides[0] if stride is None else int(stride)

@@ -65,6 +65,9 @@ int xrhip_image_render_view(xrhip_image *img, const xrhip_view_segment *segs, in
 // (likewise the Lucas-Kanade parameters: a library without the entry point tracks with the reference's constants, which is all the
 // configuration may then ask for -- Pipeline::apply_lk_params)
 int xrhip_klt_set_lk_params(xrhip_klt *ctx, const xrhip_lk_params *p) __attribute__((weak));
+// (likewise the masks: a library without them refuses a mask -- Pipeline::set_static_mask / make_image)
+int xrhip_klt_set_mask(xrhip_klt *ctx, const void *mask, int stride_bytes, int on_device) __attribute__((weak));
+int xrhip_image_set_mask(xrhip_image *img, const void *mask, int stride_bytes, int on_device) __attribute__((weak));
 // (likewise the covariance of a solved window: a library without it answers status -1 -- BaBuilder::covariance)
 int xrhip_ba_covariance(xrhip_ba *ctx, const xrhip_ba_problem *problem, const xrhip_cov_request *req) __attribute__((weak));
 }
@@ -85,6 +88,10 @@ struct FrameInput {
     int format = XRHIP_PIXFMT_GRAY8, bits = 0, limited_range = 0;
     // set: the frame is larger than cam_resolution and its crop is area-averaged down to the working plane (described by format)
     const xrhip_frame_geometry *geo = nullptr;
+    // set: the frame's own mask, W x H bytes at the working resolution (xrslam_hip.h: xrhip_image_set_mask)
+    const uint8_t *mask = nullptr;
+    int mask_stride = 0;
+    bool mask_on_device = false;
 };
 
 struct HipError : std::runtime_error {
@@ -374,6 +381,14 @@ struct Pipeline {
         }
         group = g;
     }
+    // the static mask (XRSLAMAmdSetMask): nullptr clears it
+    void set_static_mask(const void *mask, int stride, bool on_device) {
+        if (!xrhip_klt_set_mask) {
+            if (!mask) return;
+            throw std::runtime_error("Mask is not supported: this library has no xrhip_klt_set_mask");
+        }
+        hip_check(xrhip_klt_set_mask(klt, mask, stride, on_device ? 1 : 0), "xrhip_klt_set_mask");
+    }
     xrhip_image *acquire_image() {
         {
             std::lock_guard<std::mutex> lk(pool_mutex);
@@ -447,6 +462,10 @@ struct Pipeline {
         else if (und) hip_check(xrhip_image_upload_distorted(img->h, pixels, stride, dev), "xrhip_image_upload_distorted");
         else if (dev) hip_check(xrhip_image_upload_device(img->h, pixels, stride), "xrhip_image_upload_device");
         else hip_check(xrhip_image_upload(img->h, pixels, stride), "xrhip_image_upload");
+        if (in.mask) {   // the frame's own mask: bound to it here, before anything reads the frame
+            if (!xrhip_image_set_mask) throw std::runtime_error("Mask is not supported: this library has no xrhip_image_set_mask");
+            hip_check(xrhip_image_set_mask(img->h, in.mask, in.mask_stride, in.mask_on_device ? 1 : 0), "xrhip_image_set_mask");
+        }
         // FeatureTracker::work's first step (feature_tracker.cpp:39) depends on nothing but the frame: its launches are queued here,
         // behind the frame's DMA, so the device builds the pyramid while the host is still on its way to the tracker (input
         // synchronisation, frame construction, the interval's pre-integration launch).  Same call, same arguments.

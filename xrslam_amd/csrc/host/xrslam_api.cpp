@@ -25,6 +25,11 @@ struct Manager {
     std::string last_error;
     int device = -1;   // HIP device the instance was created on (the current device is a per-thread setting)
     bool bound_by_replay = false;   // inside XRSLAMAmdInstanceReplay: the device is current for the whole loop
+    // XRSLAMAmdSetNextFrameMask: waits for the next pushed camera frame (a host mask: our copy, packed; an HBM mask: the caller's)
+    bool next_mask_set = false, next_mask_on_device = false;
+    std::vector<uint8_t> next_mask_host;
+    const void *next_mask_dev = nullptr;
+    int next_mask_stride = 0;
 };
 
 Manager &mgr() {
@@ -93,8 +98,16 @@ void push_frame(Manager &m, const xrh::FrameInput &in, double t, const char *ref
     guarded(m, [&] {
         try {
             std::lock_guard<std::mutex> lk(m.input_mutex);
+            // the mask waiting for this frame goes with it, whatever becomes of the frame
+            xrh::FrameInput fin = in;
+            if (m.next_mask_set) {
+                fin.mask = m.next_mask_on_device ? static_cast<const uint8_t *>(m.next_mask_dev) : m.next_mask_host.data();
+                fin.mask_stride = m.next_mask_stride;
+                fin.mask_on_device = m.next_mask_on_device;
+                m.next_mask_set = false;
+            }
             if (refused) throw std::runtime_error(refused);
-            m.cur_image = m.sys->P.make_image(in, t);
+            m.cur_image = m.sys->P.make_image(fin, t);
         } catch (...) {
             std::lock_guard<std::mutex> lk(m.input_mutex);
             m.cur_image.reset();
@@ -317,6 +330,46 @@ void impl_flush(Manager &m) {
     if (!m.sys) return;
     bind_device(m);
     guarded(m, [&] { m.sys->sync(); });
+}
+
+// XRSLAMAmdSetMask / XRSLAMAmdSetNextFrameMask: 1, or 0 with the reason in last_error and the mask in force unchanged
+int mask_refused(Manager &m, const std::string &why) {
+    m.last_error = why;
+    std::fprintf(stderr, "[xrslam_hip] %s\n", why.c_str());
+    return 0;
+}
+int impl_set_mask(Manager &m, const void *mask, int stride, int on_device) {
+    if (!m.sys) return mask_refused(m, "XRSLAMAmdSetMask: no instance");
+    if (mask && stride < (int)m.config.cam_resolution[0]) return mask_refused(m, "XRSLAMAmdSetMask: stride < width of the working image");
+    bind_device(m);
+    int ok = 1;
+    try {   // (not guarded(): a refused mask is an answer, not a failure of the frame in flight)
+        std::lock_guard<std::mutex> lk(m.input_mutex);
+        m.sys->P.set_static_mask(mask, stride, on_device != 0);
+    } catch (const std::exception &e) {
+        ok = mask_refused(m, std::string("XRSLAMAmdSetMask: ") + e.what());
+    }
+    return ok;
+}
+int impl_set_next_frame_mask(Manager &m, const void *mask, int stride, int on_device) {
+    if (!m.sys) return mask_refused(m, "XRSLAMAmdSetNextFrameMask: no instance");
+    const int w = (int)m.config.cam_resolution[0], h = (int)m.config.cam_resolution[1];
+    if (mask && stride < w) return mask_refused(m, "XRSLAMAmdSetNextFrameMask: stride < width of the working image");
+    if (mask && !xrhip_image_set_mask) return mask_refused(m, "XRSLAMAmdSetNextFrameMask: Mask is not supported: this library has no xrhip_image_set_mask");
+    if (mask && m.sys->P.group) return mask_refused(m, "XRSLAMAmdSetNextFrameMask: the instance is a member of a group");
+    std::lock_guard<std::mutex> lk(m.input_mutex);
+    m.next_mask_set = mask != nullptr;
+    if (!mask) return 1;
+    m.next_mask_on_device = on_device != 0;
+    if (on_device) {
+        m.next_mask_dev = mask;
+        m.next_mask_stride = stride;
+    } else {   // copied now: the caller's buffer is free on return
+        m.next_mask_host.resize((size_t)w * h);
+        for (int y = 0; y < h; ++y) std::memcpy(&m.next_mask_host[(size_t)y * w], static_cast<const uint8_t *>(mask) + (size_t)y * stride, (size_t)w);
+        m.next_mask_stride = w;
+    }
+    return 1;
 }
 
 void impl_set_threading(Manager &m, int mode) {
@@ -568,6 +621,8 @@ void XRSLAMAmdGetInitReport(XRSLAMAmdInitReport *out) { impl_get_init_report(mgr
 int XRSLAMAmdGetTrackerParams(XRSLAMAmdTrackerParams *out) { return impl_get_tracker_params(mgr(), out); }
 const char *XRSLAMAmdLastError(void) { return mgr().last_error.c_str(); }
 void XRSLAMAmdSetThreading(int mode) { impl_set_threading(mgr(), mode); }
+int XRSLAMAmdSetMask(const void *mask, int stride, int on_device) { return impl_set_mask(mgr(), mask, stride, on_device); }
+int XRSLAMAmdSetNextFrameMask(const void *mask, int stride, int on_device) { return impl_set_next_frame_mask(mgr(), mask, stride, on_device); }
 void XRSLAMAmdFlush(void) { impl_flush(mgr()); }
 int XRSLAMAmdGetFeatures(XRSLAMAmdFeature *out, int cap, double *timestamp) { return impl_get_features(mgr(), out, cap, timestamp); }
 void XRSLAMAmdSetFeatureHistory(int frames) { impl_set_feature_history(mgr(), frames); }
@@ -669,6 +724,12 @@ const char *XRSLAMAmdInstanceLastError(XRSLAMAmdInstance *inst) { return inst ? 
 void XRSLAMAmdInstanceSetThreading(XRSLAMAmdInstance *inst, int mode) {
     if (inst) impl_set_threading(inst->m, mode);
 }
+int XRSLAMAmdInstanceSetMask(XRSLAMAmdInstance *inst, const void *mask, int stride, int on_device) {
+    return inst ? impl_set_mask(inst->m, mask, stride, on_device) : 0;
+}
+int XRSLAMAmdInstanceSetNextFrameMask(XRSLAMAmdInstance *inst, const void *mask, int stride, int on_device) {
+    return inst ? impl_set_next_frame_mask(inst->m, mask, stride, on_device) : 0;
+}
 void XRSLAMAmdInstanceFlush(XRSLAMAmdInstance *inst) {
     if (inst) impl_flush(inst->m);
 }
@@ -711,6 +772,7 @@ int XRSLAMAmdGroupDestroy(XRSLAMAmdGroup *grp) {
 }
 int XRSLAMAmdInstanceJoinGroup(XRSLAMAmdInstance *inst, XRSLAMAmdGroup *grp) {
     if (!inst || !inst->m.sys) return 0;
+    if (grp && inst->m.next_mask_set) return mask_refused(inst->m, "XRSLAMAmdInstanceJoinGroup: a mask is waiting for the next frame; a masked instance cannot join a group");
     int ok = 0;
     bind_device(inst->m);
     guarded(inst->m, [&] {

@@ -45,6 +45,7 @@ struct DetectPayload {
     HarrisArgs hr;
     HarrisNmsArgs nms;
     HarrisSelectArgs sel;
+    const uint8_t *mask = nullptr;   // the image's effective mask: the masked Harris kernels run (never in a group's batch)
 };
 struct TrackPayload {
     LkTrackArgs lk;
@@ -147,6 +148,10 @@ struct xrhip_klt {
     xrhip_lk_params lk{XRHIP_KLT_WIN, XRHIP_KLT_LEVELS - 1, 30, 0.01};
     bool force_general = false;   // xrhip_debug_force_general_lk
     int n_images = 0;             // images alive: their pyramid storage is sized by lk.max_level
+    // masks (xrhip_klt_set_mask / xrhip_image_set_mask): nothing of it exists before the first mask of this context
+    uint8_t *mask_static = nullptr;   // w*h bytes 0 / 1 in HBM
+    bool static_on = false;
+    bool mask_used = false;           // an image of this context has been handed a per-frame mask: the context stays out of groups
 };
 
 struct xrhip_image {
@@ -158,6 +163,10 @@ struct xrhip_image {
     int detect_seq = 0;         // != 0: the Harris pass of this image is in flight / done under that sequence number
     int levels = KLT_LEVELS;    // ctx->lk.max_level + 1 when the image was created
     LevelBuf lv[KLT_MAX_LEVELS];
+    // effective mask = static && per-frame (w*h bytes 0 / 1 in HBM; allocated by the image's first masked frame)
+    uint8_t *mask = nullptr;
+    bool mask_on = false;         // `mask` holds this frame's effective mask
+    bool mask_resolved = false;   // this frame's effective mask is decided (an upload resets it; resolve_mask decides)
 };
 
 static PyrView make_view(const xrhip_image *img) {
@@ -339,8 +348,13 @@ static void launch_detect_chunk(const DetectPayload *const *d, int m, hipStream_
         gx = std::max(gx, d[i]->hr.gx);
         gy = std::max(gy, d[i]->hr.gy);
     }
-    hipLaunchKernelGGL(k_harris, dim3(gx, gy, m), dim3(256), 0, s, bh);
-    hipLaunchKernelGGL(k_harris_nms, dim3(gx, gy, m), dim3(256), 0, s, bn);
+    if (m == 1 && d[0]->mask) {   // an image with an effective mask (its context launches for itself): the masked maximum and NMS
+        hipLaunchKernelGGL(k_harris_m, dim3(gx, gy, 1), dim3(256), 0, s, d[0]->hr, d[0]->mask);
+        hipLaunchKernelGGL(k_harris_nms_m, dim3(gx, gy, 1), dim3(256), 0, s, d[0]->nms, d[0]->mask);
+    } else {
+        hipLaunchKernelGGL(k_harris, dim3(gx, gy, m), dim3(256), 0, s, bh);
+        hipLaunchKernelGGL(k_harris_nms, dim3(gx, gy, m), dim3(256), 0, s, bn);
+    }
     hipLaunchKernelGGL(k_harris_select, dim3(1, 1, m), dim3(1024), SEL_LDS_BYTES, s, bs);
 }
 
@@ -470,6 +484,8 @@ int xrhip_klt_join_group(xrhip_klt *c, xrhip_group *g) {
         return xr_fail(XRHIP_EINVAL, "xrhip_klt_join_group: the context and the group live on different devices");
     if (g && lk_general(c))
         return xr_fail(XRHIP_ESTATE, "xrhip_klt_join_group: a context with non-default LK parameters (xrhip_klt_set_lk_params) cannot join a group");
+    if (g && (c->static_on || c->mask_used))
+        return xr_fail(XRHIP_ESTATE, "xrhip_klt_join_group: a context with a mask (xrhip_klt_set_mask / xrhip_image_set_mask) cannot join a group");
     // whatever the context has queued so far completes where it was queued
     {
         const int rc = flush_upload(c);
@@ -586,6 +602,7 @@ void xrhip_klt_destroy(xrhip_klt *c) {
     if (c->view_t1) hipEventDestroy(c->view_t1);
     hipFree(c->scale_src);
     hipFree(c->bayer_gray);
+    hipFree(c->mask_static);
     if (c->span_t0) hipEventDestroy(c->span_t0);
     if (c->span_t1) hipEventDestroy(c->span_t1);
     for (int i = 0; i < xrhip_klt::UP_SLOTS; ++i) {
@@ -641,6 +658,7 @@ void xrhip_image_destroy(xrhip_image *im) {
     if (im->ctx->group) group_drain(im->ctx->group, GQ_KLT, im->ctx);
     hipStreamSynchronize(im->ctx->stream);
     hipFree(im->raw);
+    hipFree(im->mask);
     for (int l = 0; l < im->levels; ++l) {
         hipFree(im->lv[l].img_base);
         hipFree(im->lv[l].der_base);
@@ -976,6 +994,104 @@ static int upload_frame(xrhip_image *im, const FrameSource &s, const char *bad_f
     im->have_pyramid = false;
     im->want_detect = false;
     im->detect_seq = 0;
+    im->mask_on = false;   // (a per-frame mask belonged to the frame before)
+    im->mask_resolved = false;
+    return XRHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ masks
+// One k_mask_ingest launch in the context's order: `dst` = (src != 0) && (stat != 0), either source may be missing (not both).
+// A host mask goes through the next pinned slot (packed; the caller's buffer is free on return), a mask in HBM is read where it lies.
+static int ingest_mask(xrhip_klt *c, const uint8_t *src, int stride, bool on_device, const uint8_t *stat, uint8_t *dst) {
+    MaskArgs a{src, stride, stat, dst, c->w, c->h};
+    int slot = -1;
+    if (src && !on_device) {
+        const int rc = slot_fill(c, src, stride, (size_t)c->w, c->h, slot);
+        if (rc) return rc;
+        uint8_t *dbuf = nullptr;
+        XR_HIP(hipHostGetDevicePointer((void **)&dbuf, c->up_buf[slot], 0));
+        a.src = dbuf;
+        a.sstride = c->w;
+    }
+    hipLaunchKernelGGL(k_mask_ingest, grid_of_fours((size_t)c->w * c->h), dim3(256), 0, c->stream, a);
+    XR_HIP(hipGetLastError());
+    return slot >= 0 ? slot_in_flight(c, slot) : XRHIP_OK;
+}
+static int mask_plane(const xrhip_klt *c, uint8_t *&plane) {
+    if (!plane) XR_HIP(hipMalloc(&plane, ((size_t)c->w * c->h + 3) & ~(size_t)3));
+    return XRHIP_OK;
+}
+// The frame's effective mask is decided by the first of xrhip_image_set_mask / preprocess / detect / track / xrhip_debug_get_mask after
+// its upload: a frame that was handed no per-frame mask takes the static one here -- one ingest launch per masked frame either way.
+// Without a static mask this is two flag tests: nothing is allocated, launched or copied.
+static int resolve_mask(xrhip_image *im) {
+    if (im->mask_resolved) return XRHIP_OK;
+    xrhip_klt *c = im->ctx;
+    if (c->static_on) {
+        int rc = mask_plane(c, im->mask);
+        if (rc) return rc;
+        rc = ingest_mask(c, nullptr, 0, true, c->mask_static, im->mask);
+        if (rc) return rc;
+        im->mask_on = true;
+    }
+    im->mask_resolved = true;
+    return XRHIP_OK;
+}
+static int check_mask(const char *who, const xrhip_klt *c, int stride) {
+    if (c->group) return frame_fail(XRHIP_ESTATE, who, "the context is a member of a group (its shared launches are the unmasked kernels)");
+    if ((long long)stride < (long long)c->w) return frame_fail(XRHIP_EINVAL, who, "stride_bytes < width");
+    return XRHIP_OK;
+}
+
+int xrhip_klt_set_mask(xrhip_klt *c, const void *mask, int stride, int on_device) {
+    if (!c) return xr_fail(XRHIP_EINVAL, "xrhip_klt_set_mask: null context");
+    if (!mask) {   // back to "no static mask" (frames already resolved keep theirs)
+        c->static_on = false;
+        return XRHIP_OK;
+    }
+    int rc = check_mask("xrhip_klt_set_mask", c, stride);
+    if (rc) return rc;
+    rc = mask_plane(c, c->mask_static);
+    if (rc) return rc;
+    // (in the stream's order: frames resolved so far have read the plane before it changes; the caller's HBM mask is free on return)
+    rc = ingest_mask(c, static_cast<const uint8_t *>(mask), stride, on_device != 0, nullptr, c->mask_static);
+    if (rc) return rc;
+    XR_HIP(hipStreamSynchronize(c->stream));
+    c->static_on = true;
+    return XRHIP_OK;
+}
+
+int xrhip_image_set_mask(xrhip_image *im, const void *mask, int stride, int on_device) {
+    if (!im) return xr_fail(XRHIP_EINVAL, "xrhip_image_set_mask: img is null");
+    xrhip_klt *c = im->ctx;
+    if (!mask) {   // the frame is back to the static mask alone (decided at its next use)
+        im->mask_on = false;
+        im->mask_resolved = false;
+        return XRHIP_OK;
+    }
+    int rc = check_mask("xrhip_image_set_mask", c, stride);
+    if (rc) return rc;
+    if (!im->have_raw) return xr_fail(XRHIP_ESTATE, "xrhip_image_set_mask: no image uploaded (the mask belongs to a frame)");
+    rc = mask_plane(c, im->mask);
+    if (rc) return rc;
+    rc = ingest_mask(c, static_cast<const uint8_t *>(mask), stride, on_device != 0, c->static_on ? c->mask_static : nullptr, im->mask);
+    if (rc) return rc;
+    c->mask_used = true;
+    im->mask_on = true;
+    im->mask_resolved = true;
+    return XRHIP_OK;
+}
+
+/* parity aid: the frame's effective mask, w*h bytes of 0 / 1 */
+int xrhip_debug_get_mask(xrhip_image *im, uint8_t *out) {
+    if (!im || !out) return xr_fail(XRHIP_EINVAL, "xrhip_debug_get_mask: null argument");
+    if (!im->have_raw) return xr_fail(XRHIP_ESTATE, "xrhip_debug_get_mask: no image uploaded");
+    int rc = resolve_mask(im);
+    if (rc) return rc;
+    if (!im->mask_on) return xr_fail(XRHIP_ESTATE, "xrhip_debug_get_mask: the image has no mask");
+    xrhip_klt *c = im->ctx;
+    XR_HIP(hipMemcpyAsync(out, im->mask, (size_t)c->w * c->h, hipMemcpyDeviceToHost, c->stream));
+    XR_HIP(hipStreamSynchronize(c->stream));
     return XRHIP_OK;
 }
 
@@ -1097,6 +1213,10 @@ int xrhip_image_preprocess(xrhip_image *im, double clip_limit, int tiles_x, int 
     xrhip_klt *c = im->ctx;
     const int w = c->w, h = c->h;
     if (w < 64 || h < 64) return xr_fail(XRHIP_EINVAL, "xrhip_image_preprocess: the tracker needs at least 64 pixels a side");
+    {
+        const int rc = resolve_mask(im);
+        if (rc) return rc;
+    }
     // cv::CLAHE extends a frame that is not a multiple of the grid in BOTH directions by tiles - size % tiles pixels: a direction
     // that divides gains a whole tile count when the other one does not (the tile kernel reflects whatever lies past the frame)
     const bool divides = w % tiles_x == 0 && h % tiles_y == 0;
@@ -1247,6 +1367,7 @@ static int fill_detect(xrhip_image *im, DetectPayload &d, int seq) {
     // the strongest candidates the spacing pass is handed: >= 896 (150 corners visit ~400), 8 per corner asked for beyond that
     const int keep = std::min(c->top_cap - 1024, std::max(SEL_K, c->max_points > 150 ? 8 * c->max_points : SEL_K));
     d.sel = HarrisSelectArgs{c->cand, c->cand_count, c->cand_cap, c->max_key, 1.0e-3, d_top, c->top_cap, d_sel, seq, keep, c->sel_hist};
+    d.mask = nullptr;
     return XRHIP_OK;
 }
 
@@ -1261,6 +1382,7 @@ static int launch_detect(xrhip_image *im) {
     const int seq = ++c->sel_seq;
     int rc = fill_detect(im, c->a_detect, seq);
     if (rc) return rc;
+    c->a_detect.mask = im->mask_on ? im->mask : nullptr;
     rc = klt_issue(c, c->rq_detect, GK_DETECT, &c->a_detect, launch_detect_batch);
     if (rc) return rc;
     prof.finish();
@@ -1285,7 +1407,9 @@ int xrhip_image_detect(xrhip_image *im, const double *existing_xy, int n_exist, 
     std::optional<HostProfScope> hp_gpu(std::in_place, 1, "detect: launch+D2H waits");
     bool own_launch = false;
     if (!im->detect_seq) {
-        int rc = launch_detect(im);
+        int rc = resolve_mask(im);
+        if (rc) return rc;
+        rc = launch_detect(im);
         if (rc) return rc;
         own_launch = true;
     }
@@ -1379,7 +1503,12 @@ int xrhip_image_track(const xrhip_image *cur, const xrhip_image *next, const dou
     if (n == 0) return XRHIP_OK;
     HostProfScope hp_trk(3, "track: whole call");
     xrhip_klt *c = cur->ctx;
-    int rc = ensure_points(c, n);
+    int rc = resolve_mask(const_cast<xrhip_image *>(next));
+    if (rc) return rc;
+    // `next` has an effective mask: the LK kernel runs without its completion mailbox and k_mask_gate, behind it, gates the status
+    // bytes and publishes the sequence number (cur's mask plays no part)
+    const uint8_t *const gate = next->mask_on ? next->mask : nullptr;
+    rc = ensure_points(c, n);
     if (rc) return rc;
     if (n > c->h_pts_cap) {
         if (c->h_pts) hipHostFree(c->h_pts);
@@ -1406,10 +1535,11 @@ int xrhip_image_track(const xrhip_image *cur, const xrhip_image *next, const dou
     }
     ProfScope prof(c, CAT_TRACK);
     const int seq = ++c->trk_seq;
-    c->done_base += (unsigned)n;
+    if (!gate) c->done_base += (unsigned)n;   // (the device counter moves only where the LK kernel counts its points done)
+    unsigned *const d_done = gate ? (unsigned *)nullptr : c->d_done;
     TrackPayload &tp = c->a_track;
     tp.lk = LkTrackArgs{make_view(cur), make_view(next), dv_curr, dv_next, has_guess ? 1 : 0, dv_status, n,
-                        c->profiling ? c->d_counters : (LkCounters *)nullptr, c->d_done, c->done_base, d_seq, seq};
+                        c->profiling ? c->d_counters : (LkCounters *)nullptr, d_done, c->done_base, d_seq, seq};
     static const bool no_inline = std::getenv("XRHIP_LK_NO_INLINE") != nullptr;   // development switch (A/B)
     tp.n_inline = 0;
     if (!no_inline && n <= LK_INLINE) {
@@ -1427,6 +1557,7 @@ int xrhip_image_track(const xrhip_image *cur, const xrhip_image *next, const dou
         det_seq = ++c->sel_seq;
         rc = fill_detect(const_cast<xrhip_image *>(next), tp.det, det_seq);
         if (rc) return rc;
+        tp.det.mask = gate;   // (the effective mask of `next`, staged since its upload)
     }
     if (c->group) {
         rc = klt_issue(c, c->rq_track, GK_TRACK, &tp, launch_track_batch);
@@ -1438,13 +1569,17 @@ int xrhip_image_track(const xrhip_image *cur, const xrhip_image *next, const dou
         tp.detect = false;
         if (lk_general(c)) {   // (never a member of a group) the kernel with runtime parameters; what follows the launch is unchanged
             const LkTrackGArgs ga{make_view_g(cur), make_view_g(next), lk_device_params(c), dv_curr, dv_next, has_guess ? 1 : 0, dv_status, n,
-                                  tp.lk.counters, c->d_done, c->done_base, d_seq, seq};
+                                  tp.lk.counters, d_done, c->done_base, d_seq, seq};
             hipLaunchKernelGGL(k_lk_track_g, dim3(n), dim3(LK_THREADS), 0, c->stream, ga);
             XR_HIP(hipGetLastError());
         } else {
             rc = klt_issue(c, c->rq_track, GK_TRACK, &tp, launch_track_batch);
         }
         if (rc) return rc;
+        if (gate) {
+            hipLaunchKernelGGL(k_mask_gate, dim3(1), dim3(256), 0, c->stream, gate, c->w, c->h, (const double2 *)dv_next, dv_status, n, d_seq, seq);
+            XR_HIP(hipGetLastError());
+        }
         prof.finish();
         if (with_detect) {
             ProfScope prof_d(c, CAT_DETECT);

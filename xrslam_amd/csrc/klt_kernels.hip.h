@@ -486,8 +486,11 @@ __device__ __forceinline__ float float_from_key(int k) {
 //    its neighbours lie inside the fetched rectangle for every element a valid output reads; the others are clamped into it
 //    (their values are never used).
 constexpr int HR_TW = 72, HR_TH = 20;   // pixel columns X0-4 .. X0+67 (dword-aligned), rows Y0-2 .. Y0+17
+// MASKED (k_harris_m, an image with an effective mask): the response plane is the same, only pixels whose mask byte is nonzero feed the
+// maximum -- cv::goodFeaturesToTrack's minMaxLoc(eig, mask).  With no such pixel the running maximum keeps its reset value.
+template <bool MASKED = false>
 __device__ __forceinline__ void d_harris(LevelView L, double kk, float s2, float *__restrict__ resp,
-                                         int *__restrict__ max_key) {
+                                         int *__restrict__ max_key, const uint8_t *__restrict__ mask = nullptr) {
     __shared__ short sdx[18][66];
     __shared__ short sdy[18][66];
     __shared__ uint32_t pix4[HR_TH * HR_TW / 4];
@@ -533,6 +536,7 @@ __device__ __forceinline__ void d_harris(LevelView L, double kk, float s2, float
     __syncthreads();
     const int lx = tid & 63, ly0 = tid >> 6;
     float best = -3.402823466e+38f;
+    [[maybe_unused]] bool seen = false;   // MASKED: this lane has met a visible pixel
     for (int q = 0; q < 4; ++q) {
         const int ly = ly0 + 4 * q;
         const int x = X0 + lx, y = Y0 + ly;
@@ -554,14 +558,35 @@ __device__ __forceinline__ void d_harris(LevelView L, double kk, float s2, float
             float apc = a + c;
             float r = (float)((double)t3 - kk * (double)apc * (double)apc);
             resp[(size_t)y * L.w + x] = r;
-            best = fmaxf(best, r);
+            if constexpr (MASKED) {
+                if (mask[(size_t)y * L.w + x]) {   // (a wavefront's lanes: 64 consecutive bytes of a row)
+                    best = fmaxf(best, r);
+                    seen = true;
+                }
+            } else {
+                best = fmaxf(best, r);
+            }
         }
     }
     // wavefront max, workgroup max through LDS, one atomic per workgroup
     for (int off = 32; off > 0; off >>= 1) best = fmaxf(best, __shfl_xor(best, off));
-    if ((tid & 63) == 0) wmax[tid >> 6] = best;
-    __syncthreads();
-    if (tid == 0) atomicMax(max_key, float_order_key(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))));
+    if constexpr (MASKED) {
+        // a tile without a visible pixel contributes nothing: the key of -FLT_MAX must not replace the reset value, which is how
+        // k_harris_nms_m knows that no pixel is visible at all
+        __shared__ int wseen[4];
+        const bool any = __any(seen);
+        if ((tid & 63) == 0) {
+            wmax[tid >> 6] = best;
+            wseen[tid >> 6] = any ? 1 : 0;
+        }
+        __syncthreads();
+        if (tid == 0 && (wseen[0] | wseen[1] | wseen[2] | wseen[3]))
+            atomicMax(max_key, float_order_key(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))));
+    } else {
+        if ((tid & 63) == 0) wmax[tid >> 6] = best;
+        __syncthreads();
+        if (tid == 0) atomicMax(max_key, float_order_key(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))));
+    }
 }
 struct HarrisArgs {
     LevelView L;
@@ -575,6 +600,10 @@ __global__ __launch_bounds__(256) void k_harris(Batch<HarrisArgs> b) {
     const HarrisArgs &a = b.e[blockIdx.z];
     if ((int)blockIdx.x >= a.gx || (int)blockIdx.y >= a.gy) return;
     d_harris(a.L, a.kk, a.s2, a.resp, a.max_key);
+}
+// the Harris pass of one image that has an effective mask (dense w x h bytes, 0 / 1): never batched, a masked context is in no group
+__global__ __launch_bounds__(256) void k_harris_m(HarrisArgs a, const uint8_t *__restrict__ mask) {
+    d_harris<true>(a.L, a.kk, a.s2, a.resp, a.max_key, mask);
 }
 
 struct HarrisCand {
@@ -600,14 +629,23 @@ __device__ __forceinline__ int sel_bin(float v, unsigned thr_bits) {
 // per workgroup (a per-pixel atomic on a single counter serialises at ~100
 // atomics/us on this chip).  Order is arbitrary; the host orders candidates by
 // the total order (v desc, idx desc).
+// MASKED (k_harris_nms_m): the maximum behind the threshold was taken over visible pixels only (d_harris<true>), a pixel is a candidate
+// only if its own mask byte is nonzero, and its eight neighbours are compared whether visible or not (cv::dilate of the whole plane).
+// No visible pixel at all: the maximum still has its reset key, which decodes to a NaN; nothing is a candidate, and no workgroup goes
+// on to the threshold or the histogram with it.  (k_harris_select then finds a count of 0 and an all-zero histogram, keeps nothing --
+// its own threshold bits come out of fmaxf(NaN, 1e-30f) = 1e-30f and are applied to no candidate -- and reports n_candidates = 0.)
+template <bool MASKED = false>
 __device__ __forceinline__ void d_harris_nms(const float *__restrict__ resp, int w, int h,
                                              const int *__restrict__ max_key, double quality,
                                              HarrisCand *__restrict__ cand, int *__restrict__ count,
-                                             int capacity, unsigned *__restrict__ sel_hist) {
+                                             int capacity, unsigned *__restrict__ sel_hist, const uint8_t *__restrict__ mask = nullptr) {
     __shared__ HarrisCand local[1024];
     __shared__ int nlocal;
     __shared__ int base;
     const int tid = threadIdx.x;
+    if constexpr (MASKED) {
+        if (*max_key == (int)0x80000000) return;   // (the same word for every thread: the workgroup leaves as one)
+    }
     if (tid == 0) nlocal = 0;
     __syncthreads();
     const float maxv = float_from_key(*max_key);
@@ -624,13 +662,26 @@ __device__ __forceinline__ void d_harris_nms(const float *__restrict__ resp, int
         const int gx = min(max(X0 - 1 + cx, 0), w - 1), gy = min(max(Y0 - 1 + cy, 0), h - 1);
         t[cy][cx] = resp[(size_t)gy * w + gx];
     }
-    __syncthreads();
     const int lx = tid & 63, ly0 = tid >> 6;
+    // MASKED: the mask bytes of this thread's four pixels, in the same batch of loads as the response tile (a wavefront reads 64
+    // consecutive bytes of a row).  Only a pixel's own byte is ever tested, so they stay in registers: no ring, nothing to share in LDS.
+    [[maybe_unused]] uint8_t mk[4] = {1, 1, 1, 1};
+    if constexpr (MASKED) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int x = min(X0 + lx, w - 1), y = min(Y0 + ly0 + 4 * q, h - 1);   // (clamped positions are never candidates)
+            mk[q] = mask[(size_t)y * w + x];
+        }
+    }
+    __syncthreads();
     for (int q = 0; q < 4; ++q) {
         const int ly = ly0 + 4 * q;
         const int x = X0 + lx;
         const int y = Y0 + ly;
         if (x < 1 || y < 1 || x >= w - 1 || y >= h - 1) continue;
+        if constexpr (MASKED) {
+            if (!mk[q]) continue;
+        }
         const float v = t[ly + 1][lx + 1];
         if (!(v > thr) || v == 0.f) continue;
         bool ok = v >= t[ly + 1][lx] && v >= t[ly + 1][lx + 2] && v >= t[ly][lx] && v >= t[ly][lx + 1] && v >= t[ly][lx + 2] &&
@@ -671,6 +722,9 @@ __global__ __launch_bounds__(256) void k_harris_nms(Batch<HarrisNmsArgs> b) {
     const HarrisNmsArgs &a = b.e[blockIdx.z];
     if ((int)blockIdx.x >= a.gx || (int)blockIdx.y >= a.gy) return;
     d_harris_nms(a.resp, a.w, a.h, a.max_key, a.quality, a.cand, a.count, a.capacity, a.sel_hist);
+}
+__global__ __launch_bounds__(256) void k_harris_nms_m(HarrisNmsArgs a, const uint8_t *__restrict__ mask) {
+    d_harris_nms<true>(a.resp, a.w, a.h, a.max_key, a.quality, a.cand, a.count, a.capacity, a.sel_hist, mask);
 }
 
 // The host's greedy spacing pass visits candidates in (response desc, index desc) order and normally stops
@@ -1532,6 +1586,71 @@ __global__ __launch_bounds__(256) void k_upload(Batch<UploadArgs> b) {
             a.dst[i] = a.src[y * (size_t)a.sstride + x];
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------ masks (xrhip_*_set_mask)
+// An image's effective mask: the dense w x h plane of bytes 0 / 1 that k_harris_m, k_harris_nms_m and k_mask_gate read.
+//   dst = (src != 0) && (stat != 0), a missing source (nullptr) counting as all ones
+// src: the caller's w x h bytes, any base alignment, any stride >= w -- in HBM where they lie, or in a pinned slot (packed);
+// stat: the context's static plane (dense, 0 / 1).  A lane owns four consecutive plane pixels = one dword store, and fetches the
+// aligned dwords that cover their four source bytes (k_upload's loader: neighbouring lanes read neighbouring dwords, and every fetched
+// dword holds a byte of the mask); four pixels that straddle a row end and the plane's last w * h % 4 pixels go byte by byte.
+struct MaskArgs {
+    const uint8_t *src;
+    int sstride;
+    const uint8_t *stat;
+    uint8_t *dst;
+    int w, h;
+};
+__global__ __launch_bounds__(256) void k_mask_ingest(MaskArgs a) {
+    const uint32_t w = (uint32_t)a.w, total = w * (uint32_t)a.h;
+    const uint32_t n4 = (total + 3u) >> 2;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n4; i += gridDim.x * 256u) {
+        const uint32_t p0 = i << 2;
+        const uint32_t y = p0 / w, x = p0 - y * w;
+        if (x + 4u <= w) {   // (p0 + 4 <= total follows)
+            uint32_t m = 0x01010101u;
+            if (a.src) {
+                uint32_t d[2];
+                load_dwords_unaligned<1>(reinterpret_cast<uintptr_t>(a.src + (size_t)y * (size_t)a.sstride + x), d);
+                m = ((d[0] & 0xffu) ? 1u : 0u) | ((d[0] & 0xff00u) ? 0x100u : 0u) | ((d[0] & 0xff0000u) ? 0x10000u : 0u) |
+                    ((d[0] & 0xff000000u) ? 0x1000000u : 0u);
+            }
+            if (a.stat) m &= reinterpret_cast<const uint32_t *>(a.stat)[i];
+            reinterpret_cast<uint32_t *>(a.dst)[i] = m;
+        } else {
+            const uint32_t pe = p0 + 4u < total ? p0 + 4u : total;
+            for (uint32_t p = p0; p < pe; ++p) {
+                const uint32_t py = p / w, px = p - py * w;
+                uint8_t m = 1;
+                if (a.src) m = a.src[(size_t)py * (size_t)a.sstride + px] ? 1 : 0;
+                if (a.stat) m &= a.stat[p];
+                a.dst[p] = m;
+            }
+        }
+    }
+}
+
+// The track gate of an image with an effective mask.  The mask may exist nowhere but in HBM, so the gate runs here, between the LK
+// kernel (launched without its completion mailbox: done == nullptr) and the host: a point that passed LK's own gates (status != 0) at
+// (x, y) is dropped when the mask of `next` is zero at (floor(x + 0.5), floor(y + 0.5)) -- the border gate has left that pixel inside
+// the plane; the clamp below costs nothing and keeps a wrong position from ever becoming a wrong address.  status / next: the pinned
+// point block the LK kernel has just written (kernel boundary on the same stream).  One workgroup; it publishes `seq` once every
+// lane's stores have been acknowledged.
+__global__ __launch_bounds__(256) void k_mask_gate(const uint8_t *__restrict__ mask, int w, int h, const double2 *next, uint8_t *status, int n,
+                                                   int *host_seq, int seq) {
+    for (int i = threadIdx.x; i < n; i += 256) {
+        if (!__hip_atomic_load(&status[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) continue;
+        const double x = __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long *>(&next[i].x), __ATOMIC_RELAXED,
+                                                                           __HIP_MEMORY_SCOPE_SYSTEM));
+        const double y = __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long *>(&next[i].y), __ATOMIC_RELAXED,
+                                                                           __HIP_MEMORY_SCOPE_SYSTEM));
+        const int px = min(max((int)floor(x + 0.5), 0), w - 1), py = min(max((int)floor(y + 0.5), 0), h - 1);
+        if (!mask[(size_t)py * w + px]) host_store(&status[i], (uint8_t)0);
+    }
+    host_stores_wait();
+    __syncthreads();
+    if (threadIdx.x == 0) host_store(host_seq, seq);
 }
 
 // ------------------------------------------------------------------------------- frames larger than the plane (xrhip_image_upload_scaled)

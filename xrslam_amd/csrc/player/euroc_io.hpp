@@ -13,6 +13,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -297,6 +298,53 @@ inline std::vector<uint8_t> read_file(const std::string &path) {
     }
     std::fclose(f);
     return buf;
+}
+
+// ------------------------------------------------------------------------------------------------ --mask
+// A binary PGM: "P5", width, height, maxval (<= 255: one byte per pixel) separated by white space, `#` comments to the end of their
+// line, ONE white-space byte after maxval, then width * height bytes.
+inline GrayImage decode_pgm(const std::vector<uint8_t> &file) {
+    size_t pos = 0;
+    auto token = [&]() {
+        for (;;) {
+            while (pos < file.size() && std::isspace(file[pos])) ++pos;
+            if (pos < file.size() && file[pos] == '#') {
+                while (pos < file.size() && file[pos] != '\n') ++pos;
+                continue;
+            }
+            break;
+        }
+        std::string t;
+        while (pos < file.size() && !std::isspace(file[pos]) && t.size() < 16) t.push_back((char)file[pos++]);
+        return t;
+    };
+    auto number = [&](const char *what) {
+        const std::string t = token();
+        if (t.empty() || t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos) throw std::runtime_error(std::string("pgm: bad ") + what);
+        return std::atoi(t.c_str());
+    };
+    if (token() != "P5") throw std::runtime_error("pgm: not a binary PGM (P5)");
+    GrayImage img;
+    img.w = number("width");
+    img.h = number("height");
+    const int maxval = number("maxval");
+    if (img.w < 1 || img.h < 1 || img.w > 16384 || img.h > 16384) throw std::runtime_error("pgm: bad size");
+    if (maxval < 1 || maxval > 255) throw std::runtime_error("pgm: maxval must be 1..255 (8 bits per pixel)");
+    if (pos >= file.size() || !std::isspace(file[pos])) throw std::runtime_error("pgm: no white space after maxval");
+    ++pos;
+    const size_t n = (size_t)img.w * (size_t)img.h;
+    if (file.size() - pos < n) throw std::runtime_error("pgm: file shorter than width * height bytes");
+    img.px.assign(file.begin() + (ptrdiff_t)pos, file.begin() + (ptrdiff_t)(pos + n));
+    return img;
+}
+// The player's --mask file: an 8-bit PGM (P5) or a PNG (decoded to gray), w x h pixels -- the working resolution.  A byte != 0: usable.
+inline GrayImage load_mask(const std::vector<uint8_t> &file, int w, int h) {
+    GrayImage m = file.size() >= 2 && file[0] == 'P' && file[1] == '5' ? decode_pgm(file) : decode_png(file);
+    if (m.channels != 1 || m.px.size() != (size_t)m.w * (size_t)m.h) throw std::runtime_error("mask: not an 8-bit gray image");
+    if (m.w != w || m.h != h)
+        throw std::runtime_error("mask: the file is " + std::to_string(m.w) + " x " + std::to_string(m.h) + ", the working resolution is " +
+                                 std::to_string(w) + " x " + std::to_string(h));
+    return m;
 }
 
 // -------------------------------------------------------------------------------------- undistortion

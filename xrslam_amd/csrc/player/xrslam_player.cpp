@@ -107,7 +107,7 @@ int main(int argc, char **argv) {
     }
     if (!opt.count("slam") || !opt.count("device") || !opt.count("euroc")) {
         std::fprintf(stderr, "usage: xrslam-player --slam cfg.yaml --device sensor.yaml --euroc <dir>/mav0 [--out traj.tum] "
-                             "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color] [--push-format gray16|rgb|rgba|bayer_rggb8|bayer_bggr16] [--push-scaled]\n"
+                             "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color] [--push-format gray16|rgb|rgba|bayer_rggb8|bayer_bggr16] [--push-scaled] [--mask mask.pgm|mask.png]\n"
                              "       [--cov-out FILE] [--view-out DIR [--view-every N] [--view-mode reference|age] [--view-trail K]]\n"
                              "   or: xrslam-player -sc cfg.yaml -dc sensor.yaml [--tum traj.tum] [--csv traj.csv] [-p] "
                              "euroc://<dir>/mav0 | tum://<dir>/mav0\n");
@@ -124,6 +124,16 @@ int main(int argc, char **argv) {
     } catch (const std::exception &e) {
         std::fprintf(stderr, "configuration: %s\n", e.what());
         return 1;
+    }
+    // --mask FILE: an 8-bit PGM (P5) or gray PNG at the working resolution, nonzero = usable: the static mask, set before the first frame
+    GrayImage mask;
+    if (opt.count("mask")) {
+        try {
+            mask = load_mask(read_file(opt["mask"]), (int)cfg.cam_resolution[0], (int)cfg.cam_resolution[1]);
+        } catch (const std::exception &e) {
+            std::fprintf(stderr, "--mask %s: %s\n", opt["mask"].c_str(), e.what());
+            return 1;
+        }
     }
     const std::vector<CameraRow> cam = load_camera_csv(root + "/cam0/data.csv");
     const std::vector<ImuRow> imu = load_imu_csv(root + "/imu0/data.csv");
@@ -145,6 +155,11 @@ int main(int argc, char **argv) {
     const bool device_undistort = undistort && cfg.cam_distortion_flag && !host_undistort;
     if (device_undistort) XRSLAMAmdSetDeviceUndistort(model.c_str());
     if (pipelined) XRSLAMAmdSetThreading(1);
+    if (!mask.px.empty() && XRSLAMAmdSetMask(mask.px.data(), mask.w, 0) != 1) {
+        std::fprintf(stderr, "--mask %s: %s\n", opt["mask"].c_str(), XRSLAMAmdLastError());
+        XRSLAMDestroy();
+        return 1;
+    }
     size_t seeded = 0;
     for (size_t i = 0; i < cam.size() && i < bootstrap; ++i) {
         const double t = cam[i].t + cfg.cam_time_offset;

@@ -148,6 +148,10 @@ def load(lib_path):
     lib.XRSLAMAmdSetThreading.argtypes = [C.c_int]
     lib.XRSLAMAmdSetThreading.restype = None
     lib.XRSLAMAmdFlush.restype = None
+    have_mask = hasattr(lib, "XRSLAMAmdSetMask")
+    if have_mask:   # static / per-frame masks
+        lib.XRSLAMAmdSetMask.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        lib.XRSLAMAmdSetNextFrameMask.argtypes = [C.c_void_p, C.c_int, C.c_int]
     have_cov = hasattr(lib, "XRSLAMAmdGetCovariance")
     if have_cov:   # covariance of the newest keyframe / landmark variances
         lib.XRSLAMAmdSetCovariance.argtypes = [C.c_int]
@@ -180,6 +184,9 @@ def load(lib_path):
             lib.XRSLAMAmdInstanceSetCovariance.restype = None
             lib.XRSLAMAmdInstanceGetCovariance.argtypes = [H, C.POINTER(XRSLAMAmdCovariance)]
             lib.XRSLAMAmdInstanceGetLandmarkVariances.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int]
+        if have_mask:
+            lib.XRSLAMAmdInstanceSetMask.argtypes = [H, C.c_void_p, C.c_int, C.c_int]
+            lib.XRSLAMAmdInstanceSetNextFrameMask.argtypes = [H, C.c_void_p, C.c_int, C.c_int]
         if have_view:
             lib.XRSLAMAmdInstanceGetFeatures.argtypes = [H, C.c_void_p, C.c_int, C.POINTER(C.c_double)]
             lib.XRSLAMAmdInstanceSetFeatureHistory.argtypes = [H, C.c_int]
@@ -277,6 +284,9 @@ class _Api:
             names["set_covariance"] = ("XRSLAMAmdSetCovariance", "XRSLAMAmdInstanceSetCovariance")
             names["get_covariance"] = ("XRSLAMAmdGetCovariance", "XRSLAMAmdInstanceGetCovariance")
             names["get_landmark_variances"] = ("XRSLAMAmdGetLandmarkVariances", "XRSLAMAmdInstanceGetLandmarkVariances")
+        if hasattr(lib, "XRSLAMAmdSetMask"):
+            names["set_mask"] = ("XRSLAMAmdSetMask", "XRSLAMAmdInstanceSetMask")
+            names["set_next_frame_mask"] = ("XRSLAMAmdSetNextFrameMask", "XRSLAMAmdInstanceSetNextFrameMask")
         if hasattr(lib, "XRSLAMAmdRenderTrackingView"):
             names["get_features"] = ("XRSLAMAmdGetFeatures", "XRSLAMAmdInstanceGetFeatures")
             names["set_feature_history"] = ("XRSLAMAmdSetFeatureHistory", "XRSLAMAmdInstanceSetFeatureHistory")
@@ -453,6 +463,23 @@ class Session:
         st = BaStats()
         self.api.get_ba_stats(C.byref(st), 1 if reset else 0)
         return st
+
+    @staticmethod
+    def _mask_args(mask, on_device, stride):
+        from xrslam_amd.abi import mask_args
+        h, w = (0, 0) if mask is None or on_device else mask.shape
+        return mask_args(mask, w, h, on_device, stride)
+
+    def set_mask(self, mask, on_device=False, stride=None):
+        """XRSLAMAmdSetMask: the static mask, a uint8 array [H][W] at the working resolution (or a device pointer with its stride);
+        None clears it.  -> True, or False with the reason in last_error()."""
+        ptr, stride = self._mask_args(mask, on_device, stride)
+        return self.api.set_mask(ptr, stride, 1 if on_device else 0) == 1
+
+    def set_next_frame_mask(self, mask, on_device=False, stride=None):
+        """XRSLAMAmdSetNextFrameMask: the mask of the next camera frame pushed (consumed by it)."""
+        ptr, stride = self._mask_args(mask, on_device, stride)
+        return self.api.set_next_frame_mask(ptr, stride, 1 if on_device else 0) == 1
 
     def set_covariance(self, on):
         """XRSLAMAmdSetCovariance: every window solve is followed by the covariance of its newest keyframe"""

@@ -7,7 +7,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .abi import FrameGeometry
+from .abi import FrameGeometry, mask_args
 
 
 class KltStats(C.Structure):
@@ -68,6 +68,9 @@ def _bind():
     L.xrhip_klt_set_lk_params.argtypes = [vp, C.POINTER(LkParams)]
     L.xrhip_klt_get_lk_params.argtypes = [vp, C.POINTER(LkParams)]
     L.xrhip_debug_force_general_lk.argtypes = [vp, C.c_int]
+    L.xrhip_klt_set_mask.argtypes = [vp, vp, C.c_int, C.c_int]
+    L.xrhip_image_set_mask.argtypes = [vp, vp, C.c_int, C.c_int]
+    L.xrhip_debug_get_mask.argtypes = [vp, vp]
     return L
 
 
@@ -79,6 +82,8 @@ def L():
     if _L is None:
         _L = _bind()
     return _L
+
+
 
 
 class KltContext:
@@ -152,6 +157,12 @@ class KltContext:
     def force_general_lk(self, on):
         """Parity / measurement switch: the kernels with runtime parameters also at the reference's values."""
         check(L().xrhip_debug_force_general_lk(self._h, 1 if on else 0))
+
+    def set_mask(self, mask, on_device=False, stride=None):
+        """The static mask of this context (include/xrslam_hip.h, "Masks"): nonzero bytes may be used, zero bytes are excluded from
+        detection and drop tracked points that land on them.  None clears it."""
+        ptr, stride = mask_args(mask, self.w, self.h, on_device, stride)
+        check(L().xrhip_klt_set_mask(self._h, ptr, stride, 1 if on_device else 0))
 
     def set_undistort_map(self, map2):
         """Packed 1/32-pixel inverse map [h][w][2] uint32 (include/xrslam_hip.h), or None to switch the device
@@ -259,6 +270,18 @@ class HipImage:
     def upload_scaled_distorted(self, pixels, geo, fmt=0, bits=0, limited_range=0, on_device=False, stride=None):
         """upload_scaled for a frame as the camera recorded it: scaled, then rectified (KltContext.set_undistort_map)."""
         self.upload_scaled(pixels, geo, fmt, bits, limited_range, on_device, stride, _fn="xrhip_image_upload_scaled_distorted")
+
+    def set_mask(self, mask, on_device=False, stride=None):
+        """The per-frame mask of the frame this image holds (after its upload, before preprocess / detect / track use it); combined
+        with the context's static mask by AND.  None clears it; the next upload drops it."""
+        ptr, stride = mask_args(mask, self.ctx.w, self.ctx.h, on_device, stride)
+        check(L().xrhip_image_set_mask(self._h, ptr, stride, 1 if on_device else 0))
+
+    def mask(self):
+        """The frame's effective mask, uint8 [h][w] of 0 / 1 (parity aid; an error if the image has none)."""
+        out = np.empty((self.ctx.h, self.ctx.w), np.uint8)
+        check(L().xrhip_debug_get_mask(self._h, _p(out)))
+        return out
 
     def raw(self):
         """The 8-bit frame preprocess() will read (parity aid)."""
