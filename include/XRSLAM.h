@@ -219,6 +219,36 @@ typedef struct XRSLAMAmdFrameGeometry {
 void XRSLAMAmdPushImageScaled(const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt /* NULL = GRAY8 */,
                               const XRSLAMAmdFrameGeometry *geo, int on_device, double timestamp);
 void XRSLAMAmdScaleIntrinsics(const double src[4], const XRSLAMAmdFrameGeometry *geo, int W, int H, double out[4]);
+/* Frames from a sensor mounted a quarter turn against the device, hung upside down, read out with its mirror / flip register set, or
+ * delivered by a decoder with an EXIF / display-matrix orientation: turned on the GPU as part of the frame's upload.  How the camera
+ * is mounted is a property of the instance, so the orientation is a sticky setting (default 0) that every push and replay entry point
+ * honours, XRSLAMPushSensorData(XRSLAM_SENSOR_CAMERA) included; it is bound to a frame when the frame is pushed (pipelined mode too).
+ * An orientation is o = r + 4 f, 0 .. 7, applied to the gray crop c(i, j), 0 <= i < cw, 0 <= j < ch (after format reduction /
+ * demosaicing and cropping, before scaling):
+ *   f set: mirrored left to right first     c'(i, j) = c(cw-1-i, j)
+ *   then r quarter turns CLOCKWISE          r = 1: u(X, Y) = c'(Y, ch-1-X);  r = 2: u(X, Y) = c'(cw-1-X, ch-1-Y);  r = 3: u(X, Y) = c'(cw-1-Y, X)
+ * u (ch x cw for odd r) is then scaled to the working image W x H, and rectified if device undistortion is on.  An unscaled frame is
+ * therefore H x W in memory for odd r (stride >= H * bytes per pixel); a scaled one needs W <= the turned crop's width and H <= its
+ * height.  Masks and the tracking view describe the working image and are untouched.  SetFrameOrientation returns 1, or 0 with the
+ * reason in XRSLAMAmdLastError for a value outside 0 .. 7 (the setting stays); a frame that does not fit the orientation is dropped
+ * like any other bad frame, and nothing aborts.
+ * cam0.* describe the WORKING image, as always, and the library does not rewrite the configuration.  Two helpers, pure host code:
+ *   XRSLAMAmdOrientationFromExif  EXIF tag 274 -> o:  1->0, 6->1, 3->2, 8->3, 2->4, 7->5, 4->6, 5->7;  -1 for a value outside 1 .. 8.
+ *   XRSLAMAmdOrientIntrinsics     maps the source camera's {fx, fy, cx, cy} through crop, orientation and scale (pixel centres at
+ *     integer coordinates; geo NULL: the whole frame, W x H, or H x W for odd r).  A crop pixel (i, j) = (u - crop_x, v - crop_y)
+ *     lands at (X, Y) in u:  i' = f ? cw-1-i : i;  r = 0: (i', j);  1: (ch-1-j, i');  2: (cw-1-i', ch-1-j);  3: (j, cw-1-i').
+ *     That map is (X, Y)^T = P (i, j)^T + t with P a signed permutation; with (tw, th) = u's size, sx = W/tw, sy = H/th:
+ *       (fx', fy') = (sx, sy) * |P| (fx, fy)      (fx and fy change places for odd r)
+ *       (cx', cy') = (sx, sy) * (P (cx - crop_x, cy - crop_y)^T + t + 0.5) - 0.5
+ *     R (row-major 3 x 3) = [P 0; 0 1] takes a ray of the source camera to the working camera's: a rotation about the optical axis, a
+ *     reflection for f = 1; the caller composes it into cam0.extrinsic.  Returns 1, or 0 for a bad argument (nothing written).
+ * Limit: distortion coefficients belong to the working image.  Radial terms survive a turn (they depend on the radius alone),
+ * tangential ones (p1, p2) do not, and the library does not convert them. */
+int XRSLAMAmdSetFrameOrientation(int orientation);
+int XRSLAMAmdGetFrameOrientation(void);
+int XRSLAMAmdOrientationFromExif(int exif);
+int XRSLAMAmdOrientIntrinsics(const double src[4], const XRSLAMAmdFrameGeometry *geo /* NULL: whole frame */, int orientation, int W, int H,
+                              double out[4], double R[9]);
 /* What the reference's dataset readers ask the YamlConfig* for (xrslam-pc/player/src/IO/euroc_dataset_reader.cpp:4-7,16,62-66;
  * tum_dataset_reader.cpp:4-6,67-76): camera_time_offset(), camera_distortion_flag(), camera_distortion(),
  * camera_intrinsic(), camera_resolution().  The `config` out-parameter of XRSLAMCreate is an opaque handle here (the
@@ -412,6 +442,8 @@ void XRSLAMAmdInstancePushImageFormat(XRSLAMAmdInstance *inst, const void *pixel
                                       int on_device, double timestamp);
 void XRSLAMAmdInstancePushImageScaled(XRSLAMAmdInstance *inst, const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt,
                                       const XRSLAMAmdFrameGeometry *geo, int on_device, double timestamp);
+int XRSLAMAmdInstanceSetFrameOrientation(XRSLAMAmdInstance *inst, int orientation);
+int XRSLAMAmdInstanceGetFrameOrientation(XRSLAMAmdInstance *inst);
 void XRSLAMAmdInstanceGetCameraConfig(XRSLAMAmdInstance *inst, XRSLAMAmdCameraConfig *out);
 int XRSLAMAmdInstanceDescribeConfig(XRSLAMAmdInstance *inst, char *buf, int cap);
 void XRSLAMAmdInstanceSetDeviceUndistort(XRSLAMAmdInstance *inst, const char *model);

@@ -182,6 +182,26 @@ int xrhip_image_upload_scaled(xrhip_image *img, const void *pixels, int stride_b
                               int on_device, const xrhip_frame_geometry *geo);
 int xrhip_image_upload_scaled_distorted(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits, int limited_range,
                                         int on_device, const xrhip_frame_geometry *geo);
+/* Frames from a sensor that is mounted turned or read out mirrored: a sticky setting of the context, in force from the next upload on.
+ * An orientation is o = r + 4 f, 0 .. 7 (0: none, the default).  It acts on the gray crop c(i, j), 0 <= i < cw, 0 <= j < ch -- after
+ * format reduction / demosaicing and cropping, before scaling:
+ *   f set: mirrored left to right first       c'(i, j) = c(cw-1-i, j)      (else c' = c)
+ *   then r quarter turns CLOCKWISE            r = 1: u(X, Y) = c'(Y, ch-1-X)        u is ch x cw
+ *                                             r = 2: u(X, Y) = c'(cw-1-X, ch-1-Y)
+ *                                             r = 3: u(X, Y) = c'(cw-1-Y, X)        u is ch x cw
+ * The turned crop u is area-scaled to the W x H plane as defined above (ratio 1: a copy); device undistortion comes after that; masks
+ * and the tracking view describe the working image and are untouched.  (Exact area scaling commutes with the eight orientations: the
+ * implementation reduces / demosaics / scales in the source's orientation and turns the working-size result, one launch of k_orient.)
+ * Every xrhip_image_upload* then reads its frame as turned: an unscaled frame is H x W in memory for odd r (stride_bytes >= the
+ * frame's own row: H * bytes per pixel); a scaled one needs W <= the TURNED crop's width and H <= its height (odd r: W <= crop_height,
+ * H <= crop_width); stride, crop origin, Bayer phase and Bayer edge mirroring mean what they meant, in source coordinates, and only
+ * the crop's bytes are read.  A bad value (XRHIP_EINVAL) leaves the setting as it was; a frame whose stride or geometry does not fit
+ * is refused like any other (XRHIP_EINVAL, the image and the setting stay).  With orientation 0 nothing changes: the same launches,
+ * allocations and bits.  A member of a group: the turn is a launch of its own in the member's order, results as in a solo run.
+ * Distortion coefficients behind an undistortion map belong to the working image (radial terms survive a turn, tangential ones do
+ * not); nothing here converts them. */
+int xrhip_klt_set_orientation(xrhip_klt *ctx, int orientation);
+int xrhip_klt_get_orientation(const xrhip_klt *ctx, int *orientation);
 /* measurement aid: HIP-event time, in ms, of what the context issues between a call with phase 0 and one with phase 1 (each waits
  * for the context's queue; `ms` is written by phase 1) */
 int xrhip_debug_stream_span(xrhip_klt *ctx, int phase, double *ms);

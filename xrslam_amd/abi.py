@@ -192,6 +192,22 @@ class FrameGeometry(C.Structure):
                 ("crop_height", C.c_int)]
 
 
+# Frame orientations (xrhip_klt_set_orientation = XRSLAMAmdSetFrameOrientation): o = r + 4 f -- mirrored left to right first if f, then r
+# quarter turns clockwise
+ORIENT_NONE, ORIENT_ROT90, ORIENT_ROT180, ORIENT_ROT270, ORIENT_FLIP, ORIENT_FLIP_ROT90, ORIENT_FLIP_ROT180, ORIENT_FLIP_ROT270 = range(8)
+ORIENT_NAMES = {"none": 0, "rot90": 1, "rot180": 2, "rot270": 3, "flip": 4, "flip-rot90": 5, "flip-rot180": 6, "flip-rot270": 7,
+                "transverse": 5, "flipv": 6, "transpose": 7}
+
+
+def orientation(o):
+    """An orientation given as 0..7 or by name (ORIENT_NAMES) -> 0..7"""
+    if isinstance(o, str):
+        if o not in ORIENT_NAMES and not (o.isdigit() and int(o) < 8):
+            raise ValueError("orientation %r is not one of %s or 0..7" % (o, ", ".join(ORIENT_NAMES)))
+        return ORIENT_NAMES[o] if o in ORIENT_NAMES else int(o)
+    return int(o)
+
+
 def mask_args(mask, w, h, on_device=False, stride=None):
     """-> (pointer, row stride in bytes) of a w x h byte mask for xrhip_klt_set_mask / xrhip_image_set_mask / XRSLAMAmdSetMask /
     XRSLAMAmdSetNextFrameMask: None (clears), a uint8 array [h][w] whose rows may be strided (the caller keeps it alive for the call), or

@@ -68,6 +68,8 @@ int xrhip_klt_set_lk_params(xrhip_klt *ctx, const xrhip_lk_params *p) __attribut
 // (likewise the masks: a library without them refuses a mask -- Pipeline::set_static_mask / make_image)
 int xrhip_klt_set_mask(xrhip_klt *ctx, const void *mask, int stride_bytes, int on_device) __attribute__((weak));
 int xrhip_image_set_mask(xrhip_image *img, const void *mask, int stride_bytes, int on_device) __attribute__((weak));
+// (likewise the frame orientation: Pipeline::make_image turns such frames with pixel_format.hpp's orient_plane)
+int xrhip_klt_set_orientation(xrhip_klt *ctx, int orientation) __attribute__((weak));
 // (likewise the covariance of a solved window: a library without it answers status -1 -- BaBuilder::covariance)
 int xrhip_ba_covariance(xrhip_ba *ctx, const xrhip_ba_problem *problem, const xrhip_cov_request *req) __attribute__((weak));
 }
@@ -88,6 +90,8 @@ struct FrameInput {
     int format = XRHIP_PIXFMT_GRAY8, bits = 0, limited_range = 0;
     // set: the frame is larger than cam_resolution and its crop is area-averaged down to the working plane (described by format)
     const xrhip_frame_geometry *geo = nullptr;
+    // the frame is turned / mirrored against the working image (xrslam_hip.h: xrhip_klt_set_orientation; XRSLAMAmdSetFrameOrientation)
+    int orientation = 0;
     // set: the frame's own mask, W x H bytes at the working resolution (xrslam_hip.h: xrhip_image_set_mask)
     const uint8_t *mask = nullptr;
     int mask_stride = 0;
@@ -410,9 +414,16 @@ struct Pipeline {
     // The frame's format is resolved and validated once; the frame then goes to the one upload of xrslam_hip.h that takes it as it is.
     // Where the library behind that header lacks that upload (the CPU reference build has the gray ones only: its host arithmetic is what
     // the device's is compared against), the frame is first scaled / reduced here with the same integer formulas (pixel_format.hpp).
-    std::vector<uint8_t> gray_scratch;
+    std::vector<uint8_t> gray_scratch, turn_scratch;
+    int klt_orientation = 0;   // what the context's orientation was last set to
     std::shared_ptr<HipImage> make_image(const FrameInput &in, double t) {
         const int cols = (int)config.cam_resolution[0], rows = (int)config.cam_resolution[1];
+        // the frame as it lies in memory: turned frames (in.orientation) are rows x cols for odd quarter turns
+        const int o = in.orientation;
+        if (!orientation_valid(o)) throw std::runtime_error("Frame orientation is not supported: must be 0..7");
+        const int fcols = (o & 1) ? rows : cols, frows = (o & 1) ? cols : rows;
+        const bool host_turn = o != 0 && !xrhip_klt_set_orientation;
+        if (host_turn && in.on_device) throw std::runtime_error("Frame orientation is not supported: this library cannot turn a frame in device memory");
         PixelFormat pf;
         if (in.geo || in.by_format) {
             if (const char *why = describe_pixel_format(in.format, in.bits, in.limited_range, pf))
@@ -423,24 +434,30 @@ struct Pipeline {
         }
         if (in.geo) {
             if (!in.pixels) throw std::runtime_error("Image geometry is not supported: null pixels");
-            if (const char *why = check_frame_geometry(in.geo, cols, rows, pf.bpp, in.stride))
+            if (const char *why = check_frame_geometry(in.geo, fcols, frows, pf.bpp, in.stride))
                 throw std::runtime_error(std::string("Image geometry is not supported: ") + why);
-        } else if (in.by_format && (!in.pixels || (long long)in.stride < (long long)cols * pf.bpp)) {
+        } else if (in.by_format && (!in.pixels || (long long)in.stride < (long long)fcols * pf.bpp)) {
             throw std::runtime_error("Image format is not supported: null pixels or stride < width * bytes per pixel");
         }
         // the upload that takes the frame: SCALED and FORMAT carry format / bits / limited_range, COLOR carries the channels
         enum { GRAY, COLOR, FORMAT, SCALED } how = in.geo ? SCALED : pf.bpp == 2 || pf.rgb || pf.limited || pf.bayer ? FORMAT : pf.bpp != 1 ? COLOR : GRAY;
         const uint8_t *pixels = in.pixels;
         int stride = in.stride;
-        if (how == SCALED ? !have_scaled_upload() : how == FORMAT ? !have_format_upload() : how == COLOR && !have_color_upload()) {
+        if ((how == SCALED ? !have_scaled_upload() : how == FORMAT ? !have_format_upload() : how == COLOR && !have_color_upload()) || host_turn) {
             if (how == SCALED && in.on_device) throw std::runtime_error("Image geometry is not supported: this library cannot scale a frame in device memory");
+            if (host_turn && (!pixels || (how != SCALED && (long long)stride < (long long)fcols * pf.bpp))) throw std::runtime_error("Image is not supported: null pixels or stride < width * bytes per pixel");
             gray_scratch.resize((size_t)cols * rows);
             if (how == SCALED)
-                scale_frame(gray_scratch.data(), cols, rows, crop_origin(pixels, stride, *in.geo, pf.bpp), stride, in.geo->crop_width, in.geo->crop_height,
+                scale_frame(gray_scratch.data(), fcols, frows, crop_origin(pixels, stride, *in.geo, pf.bpp), stride, in.geo->crop_width, in.geo->crop_height,
                             crop_pixel_format(pf, *in.geo));
-            else reduce_frame(gray_scratch.data(), pixels, stride, cols, rows, pf);   // BGR(A): cv::cvtColor BGR(A)2GRAY, (B*1868 + G*9617 + R*4899 + 8192) >> 14
+            else reduce_frame(gray_scratch.data(), pixels, stride, fcols, frows, pf);   // BGR(A): cv::cvtColor BGR(A)2GRAY, (B*1868 + G*9617 + R*4899 + 8192) >> 14
+            if (host_turn) {   // (scaling commutes with the orientations: the working-size plane is turned)
+                turn_scratch.resize(gray_scratch.size());
+                orient_plane(turn_scratch.data(), gray_scratch.data(), fcols, frows, o);
+                gray_scratch.swap(turn_scratch);
+            }
             pixels = gray_scratch.data();
-            stride = cols;
+            stride = host_turn ? cols : fcols;
             how = GRAY;
         }
         auto img = std::make_shared<HipImage>();
@@ -453,6 +470,11 @@ struct Pipeline {
         if (group) xrhip_klt_frame_gate(klt);
         const int dev = in.on_device ? 1 : 0;
         const bool und = undistort_on_device;
+        // the orientation travels with the frame: set for this upload (a sticky setting of the context, which this pipeline alone drives)
+        if (xrhip_klt_set_orientation && (o != 0 || klt_orientation != 0)) {
+            hip_check(xrhip_klt_set_orientation(klt, o), "xrhip_klt_set_orientation");
+            klt_orientation = o;
+        }
         if (how == SCALED && und) hip_check(xrhip_image_upload_scaled_distorted(img->h, pixels, stride, in.format, in.bits, in.limited_range, dev, in.geo), "xrhip_image_upload_scaled_distorted");
         else if (how == SCALED) hip_check(xrhip_image_upload_scaled(img->h, pixels, stride, in.format, in.bits, in.limited_range, dev, in.geo), "xrhip_image_upload_scaled");
         else if (how == FORMAT && und) hip_check(xrhip_image_upload_format_distorted(img->h, pixels, stride, in.format, in.bits, in.limited_range, dev), "xrhip_image_upload_format_distorted");

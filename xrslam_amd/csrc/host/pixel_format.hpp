@@ -11,6 +11,7 @@
 //                                                  needs the pixel's neighbours: bayer_gray below, a whole frame at a time
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -202,6 +203,57 @@ inline void scale_intrinsics(const double src[4], const xrhip_frame_geometry &g,
     const double fx = src[0] * sx, fy = src[1] * sy;
     const double cx = (src[2] + 0.5 - g.crop_x) * sx - 0.5, cy = (src[3] + 0.5 - g.crop_y) * sy - 0.5;
     out[0] = fx; out[1] = fy; out[2] = cx; out[3] = cy;
+}
+
+// ------------------------------------------------------------------------------------------------ turned and mirrored frames
+// An orientation (xrslam_hip.h: xrhip_klt_set_orientation) is o = r + 4 f, 0..7: the cw x ch gray crop is mirrored left to right if f,
+// then turned r quarter turns clockwise; the turned crop (ch x cw for odd r) is what is scaled to the plane.
+inline bool orientation_valid(int o) { return o >= 0 && o <= 7; }
+inline int orientation_from_exif(int exif) {   // EXIF tag 274
+    static const int table[9] = {-1, 0, 4, 2, 6, 7, 1, 5, 3};
+    return exif >= 1 && exif <= 8 ? table[exif] : -1;
+}
+// Where pixel (i, j) of the cw x ch crop lies in the turned crop
+inline void orient_point(int o, int cw, int ch, long long i, long long j, long long &X, long long &Y) {
+    if (o & 4) i = cw - 1 - i;
+    switch (o & 3) {
+        case 0: X = i; Y = j; break;
+        case 1: X = ch - 1 - j; Y = i; break;
+        case 2: X = cw - 1 - i; Y = ch - 1 - j; break;
+        default: X = j; Y = cw - 1 - i; break;
+    }
+}
+// The dense gray plane `src` (sw x sh, the source's orientation) turned into the dense plane `dst` (sh x sw for odd r): what the
+// device's k_orient computes, for a build without it
+inline void orient_plane(uint8_t *dst, const uint8_t *src, int sw, int sh, int o) {
+    const int W = (o & 1) ? sh : sw;
+    for (int j = 0; j < sh; ++j)
+        for (int i = 0; i < sw; ++i) {
+            long long X, Y;
+            orient_point(o, sw, sh, i, j, X, Y);
+            dst[(size_t)Y * W + (size_t)X] = src[(size_t)j * sw + i];
+        }
+}
+// Intrinsics {fx, fy, cx, cy} of the source frame -> those of the W x H working plane through crop (g; nullptr: the whole frame, which
+// is H x W for odd r), orientation and scale, pixel centres at integer coordinates (XRSLAM.h: XRSLAMAmdOrientIntrinsics has the
+// formulas).  R, row-major 3 x 3: a ray of the source camera -> the working camera's.
+inline void orient_intrinsics(const double src[4], const xrhip_frame_geometry *g, int o, int W, int H, double out[4], double R[9]) {
+    const int cw = g ? g->crop_width : (o & 1) ? H : W, ch = g ? g->crop_height : (o & 1) ? W : H;
+    const double x0 = g ? g->crop_x : 0, y0 = g ? g->crop_y : 0;
+    // (X, Y) = P (i, j) + t, from the images of (0, 0), (1, 0) and (0, 1)
+    long long tx, ty, ax, ay, bx, by;
+    orient_point(o, cw, ch, 0, 0, tx, ty);
+    orient_point(o, cw, ch, 1, 0, ax, ay);
+    orient_point(o, cw, ch, 0, 1, bx, by);
+    const double P[2][2] = {{(double)(ax - tx), (double)(bx - tx)}, {(double)(ay - ty), (double)(by - ty)}};
+    const double sx = (double)W / ((o & 1) ? ch : cw), sy = (double)H / ((o & 1) ? cw : ch);
+    const double ci = src[2] - x0, cj = src[3] - y0;
+    out[0] = sx * (std::abs(P[0][0]) * src[0] + std::abs(P[0][1]) * src[1]);
+    out[1] = sy * (std::abs(P[1][0]) * src[0] + std::abs(P[1][1]) * src[1]);
+    out[2] = sx * (P[0][0] * ci + P[0][1] * cj + (double)tx + 0.5) - 0.5;
+    out[3] = sy * (P[1][0] * ci + P[1][1] * cj + (double)ty + 0.5) - 0.5;
+    const double r[9] = {P[0][0], P[0][1], 0, P[1][0], P[1][1], 0, 0, 0, 1};
+    std::memcpy(R, r, sizeof(r));
 }
 
 }   // namespace xrh

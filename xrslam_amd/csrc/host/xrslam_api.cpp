@@ -8,6 +8,7 @@
 // An instance may be driven by one thread at a time; different instances may be driven by different threads.
 #include "../../../include/XRSLAM.h"
 
+#include <atomic>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -30,6 +31,8 @@ struct Manager {
     std::vector<uint8_t> next_mask_host;
     const void *next_mask_dev = nullptr;
     int next_mask_stride = 0;
+    // XRSLAMAmdSetFrameOrientation: how the camera is mounted; every pushed frame takes the value in force when it is pushed
+    std::atomic<int> orientation{0};
 };
 
 Manager &mgr() {
@@ -74,6 +77,7 @@ int impl_create(Manager &m, const char *slam_config_path, const char *device_con
     int ok = 0;
     if (xrhip_get_device(&m.device) != 0) m.device = -1;
     m.last_error.clear();   // XRSLAMAmdLastError speaks about the instance being created, not about an earlier one
+    m.orientation.store(0);   // (likewise the frame orientation: a new instance starts with upright frames)
     guarded(m, [&] {
         {   // a second Create without Destroy: drop the previous instance first, in XRSLAMDestroy's order -- the pending
             // image returns its device buffer to the Pipeline that owns it, which must still be alive at that point
@@ -100,6 +104,7 @@ void push_frame(Manager &m, const xrh::FrameInput &in, double t, const char *ref
             std::lock_guard<std::mutex> lk(m.input_mutex);
             // the mask waiting for this frame goes with it, whatever becomes of the frame
             xrh::FrameInput fin = in;
+            fin.orientation = m.orientation.load();
             if (m.next_mask_set) {
                 fin.mask = m.next_mask_on_device ? static_cast<const uint8_t *>(m.next_mask_dev) : m.next_mask_host.data();
                 fin.mask_stride = m.next_mask_stride;
@@ -291,6 +296,17 @@ void impl_push_image_scaled(Manager &m, const void *pixels, int stride, const XR
     const xrhip_frame_geometry g = geo ? to_inner(*geo) : xrhip_frame_geometry{};
     push_frame(m, frame_input(pixels, stride, on_device, 1, fmt, &g), timestamp,
                geo && pixels ? nullptr : "Image geometry is not supported: null pixels or geometry");
+}
+
+// A value outside 0..7 is reported and the setting stays; nothing aborts and no frame is touched.
+int impl_set_frame_orientation(Manager &m, int o) {
+    if (!xrh::orientation_valid(o)) {
+        m.last_error = "Frame orientation is not supported: " + std::to_string(o) + " is not 0..7 (quarter turns clockwise + 4 * mirrored)";
+        std::fprintf(stderr, "[xrslam_hip] %s\n", m.last_error.c_str());
+        return 0;
+    }
+    m.orientation.store(o);
+    return 1;
 }
 
 void impl_get_camera_config(Manager &m, XRSLAMAmdCameraConfig *out) {
@@ -604,6 +620,15 @@ void XRSLAMAmdScaleIntrinsics(const double src[4], const XRSLAMAmdFrameGeometry 
     if (!src || !geo || !out || W < 1 || H < 1 || geo->crop_width < 1 || geo->crop_height < 1) return;
     xrh::scale_intrinsics(src, to_inner(*geo), W, H, out);
 }
+int XRSLAMAmdSetFrameOrientation(int orientation) { return impl_set_frame_orientation(mgr(), orientation); }
+int XRSLAMAmdGetFrameOrientation(void) { return mgr().orientation.load(); }
+int XRSLAMAmdOrientationFromExif(int exif) { return xrh::orientation_from_exif(exif); }
+int XRSLAMAmdOrientIntrinsics(const double src[4], const XRSLAMAmdFrameGeometry *geo, int orientation, int W, int H, double out[4], double R[9]) {
+    if (!src || !out || !R || W < 1 || H < 1 || !xrh::orientation_valid(orientation) || (geo && (geo->crop_width < 1 || geo->crop_height < 1))) return 0;
+    const xrhip_frame_geometry g = geo ? to_inner(*geo) : xrhip_frame_geometry{};
+    xrh::orient_intrinsics(src, geo ? &g : nullptr, orientation, W, H, out, R);
+    return 1;
+}
 void XRSLAMAmdPushImageFormat(const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt, int on_device, double timestamp) {
     impl_push_image_format(mgr(), pixels, stride, fmt, on_device, timestamp);
 }
@@ -679,6 +704,10 @@ void XRSLAMAmdInstancePushImageFormat(XRSLAMAmdInstance *inst, const void *pixel
                                       int on_device, double timestamp) {
     if (inst) impl_push_image_format(inst->m, pixels, stride, fmt, on_device, timestamp);
 }
+int XRSLAMAmdInstanceSetFrameOrientation(XRSLAMAmdInstance *inst, int orientation) {
+    return inst ? impl_set_frame_orientation(inst->m, orientation) : 0;
+}
+int XRSLAMAmdInstanceGetFrameOrientation(XRSLAMAmdInstance *inst) { return inst ? inst->m.orientation.load() : 0; }
 void XRSLAMAmdInstanceGetCameraConfig(XRSLAMAmdInstance *inst, XRSLAMAmdCameraConfig *out) {
     if (inst) impl_get_camera_config(inst->m, out);
 }

@@ -143,6 +143,10 @@ struct xrhip_klt {
     // is demosaiced into this cw x ch gray scratch, which k_upload_scaled then reads.  Allocated by the first scaled Bayer frame.
     uint8_t *bayer_gray = nullptr;
     size_t bayer_gray_cap = 0;
+    // turned and mirrored frames (xrhip_klt_set_orientation): o = r + 4 f; the frame's gray plane in the source's orientation (w x h, or
+    // h x w for odd r), which k_orient turns into the plane.  Allocated by the first frame uploaded with a non-zero orientation.
+    int orient = 0;
+    uint8_t *orient_src = nullptr;
     hipEvent_t span_t0 = nullptr, span_t1 = nullptr;   // xrhip_debug_stream_span
     // LK parameters (xrhip_klt_set_lk_params): at the reference's values, with the switch off, the specialised kernels run
     xrhip_lk_params lk{XRHIP_KLT_WIN, XRHIP_KLT_LEVELS - 1, 30, 0.01};
@@ -602,6 +606,7 @@ void xrhip_klt_destroy(xrhip_klt *c) {
     if (c->view_t1) hipEventDestroy(c->view_t1);
     hipFree(c->scale_src);
     hipFree(c->bayer_gray);
+    hipFree(c->orient_src);
     hipFree(c->mask_static);
     if (c->span_t0) hipEventDestroy(c->span_t0);
     if (c->span_t1) hipEventDestroy(c->span_t1);
@@ -711,6 +716,7 @@ struct FrameSource {
     bool on_device;        // pixels lie in HBM and are read where they lie
     const xrhip_frame_geometry *geo;
     bool scaled;           // larger than the plane: the crop of `geo` is area-averaged down (geo == nullptr is then an error)
+    int pw = 0, ph = 0;    // the plane as the frame sees it (upload_frame): w x h, or h x w under an orientation with odd r
 };
 static FrameSource frame_source(const void *pixels, int stride, int on_device, const xrhip_frame_geometry *geo = nullptr, bool scaled = false) {
     return FrameSource{static_cast<const uint8_t *>(pixels), stride, xrh::PixelFormat(), on_device != 0, geo, scaled};
@@ -727,9 +733,11 @@ static int check_frame(const char *who, const xrhip_image *im, const FrameSource
     if (!s.pixels) return frame_fail(XRHIP_EINVAL, who, "pixels is null");
     if (bad_format) return frame_fail(XRHIP_EINVAL, who, bad_format);
     if (s.scaled) {
-        if (const char *why = xrh::check_frame_geometry(s.geo, im->ctx->w, im->ctx->h, s.pf.bpp, s.stride)) return frame_fail(XRHIP_EINVAL, who, why);
-    } else if ((long long)s.stride < (long long)im->ctx->w * s.pf.bpp) {
-        return frame_fail(XRHIP_EINVAL, who, "stride_bytes < width * bytes per pixel");
+        if (const char *why = xrh::check_frame_geometry(s.geo, s.pw, s.ph, s.pf.bpp, s.stride))
+            return frame_fail(XRHIP_EINVAL, who, s.pw == im->ctx->w ? why : (std::string(why) + " (orientation: the frame is turned, the crop must cover height x width)").c_str());
+    } else if ((long long)s.stride < (long long)s.pw * s.pf.bpp) {
+        return frame_fail(XRHIP_EINVAL, who, s.pw == im->ctx->w ? "stride_bytes < width * bytes per pixel"
+                                                                 : "stride_bytes < height * bytes per pixel (orientation: the frame is height x width in memory)");
     }
     return XRHIP_OK;
 }
@@ -817,28 +825,28 @@ static int queue_upload(xrhip_klt *c, const UploadArgs &a) {
     c->a_upload = a;
     return klt_issue(c, c->rq_upload, GK_UPLOAD, &c->a_upload, launch_upload_batch);
 }
-// A frame of the plane's size into `dst` (w*h, dense).  8-bit gray on a context of its own is a copy: DMA from the pinned slot, or
+// A frame of the plane's size into `dst` (s.pw * s.ph, dense).  8-bit gray on a context of its own is a copy: DMA from the pinned slot, or
 // device to device.  Everything else is a k_upload request (fmt: UPF_*), which reduces the other formats to gray as it reads -- a host
 // frame from the mapped slot, so the plane in HBM is written once and the frame's bytes cross the host link once.
 static int upload_into(xrhip_klt *c, const FrameSource &s, uint8_t *dst) {
     const int bpp = s.pf.bpp, fmt = upf_word(s.pf);
     const bool copy = !c->group && bpp == 1 && fmt == 0;
     if (s.on_device) {
-        if (!copy) return queue_upload(c, UploadArgs{s.pixels, s.stride, dst, c->w, c->h, bpp, fmt});
-        XR_HIP(hipMemcpy2DAsync(dst, c->w, s.pixels, s.stride, c->w, c->h, hipMemcpyDeviceToDevice, c->stream));
+        if (!copy) return queue_upload(c, UploadArgs{s.pixels, s.stride, dst, s.pw, s.ph, bpp, fmt});
+        XR_HIP(hipMemcpy2DAsync(dst, s.pw, s.pixels, s.stride, s.pw, s.ph, hipMemcpyDeviceToDevice, c->stream));
         return XRHIP_OK;
     }
-    const size_t row = (size_t)c->w * bpp;
+    const size_t row = (size_t)s.pw * bpp;
     int slot = 0;
-    int rc = slot_fill(c, s.pixels, s.stride, row, c->h, slot);
+    int rc = slot_fill(c, s.pixels, s.stride, row, s.ph, slot);
     if (rc) return rc;
     uint8_t *buf = c->up_buf[slot];
     if (copy) {
-        XR_HIP(hipMemcpyAsync(dst, buf, row * c->h, hipMemcpyHostToDevice, c->stream));
+        XR_HIP(hipMemcpyAsync(dst, buf, row * s.ph, hipMemcpyHostToDevice, c->stream));
     } else {
         uint8_t *dbuf = nullptr;
         XR_HIP(hipHostGetDevicePointer((void **)&dbuf, buf, 0));
-        rc = queue_upload(c, UploadArgs{dbuf, (int)row, dst, c->w, c->h, bpp, fmt});
+        rc = queue_upload(c, UploadArgs{dbuf, (int)row, dst, s.pw, s.ph, bpp, fmt});
         if (rc) return rc;
     }
     return slot_in_flight(c, slot);
@@ -856,19 +864,19 @@ static int grow_scratch(xrhip_klt *c, uint8_t *&buf, size_t &cap, size_t bytes) 
     cap = bytes;
     return XRHIP_OK;
 }
-// k_upload_scaled's arguments: the cw x ch crop at `src` (bpp, fmt: as UploadArgs) down to the context's plane at `dst`
-static ScaleArgs scale_args(const xrhip_klt *c, const uint8_t *src, int stride, int bpp, int fmt, int cw, int ch, uint8_t *dst) {
+// k_upload_scaled's arguments: the cw x ch crop at `src` (bpp, fmt: as UploadArgs) down to the w x h plane at `dst`
+static ScaleArgs scale_args(int w, int h, const uint8_t *src, int stride, int bpp, int fmt, int cw, int ch, uint8_t *dst) {
     ScaleArgs a{};
     a.src = src;
     a.sstride = stride;
     a.dst = dst;
-    a.w = c->w;
-    a.h = c->h;
+    a.w = w;
+    a.h = h;
     a.bpp = bpp;
     a.fmt = fmt;
     a.cw = cw;
     a.ch = ch;
-    a.wide = ((uint64_t)c->w * (uint64_t)cw >> 32) != 0 || ((uint64_t)c->h * (uint64_t)ch >> 32) != 0;
+    a.wide = ((uint64_t)w * (uint64_t)cw >> 32) != 0 || ((uint64_t)h * (uint64_t)ch >> 32) != 0;
     return a;
 }
 static dim3 grid_of_fours(size_t pixels) {   // a lane owns four plane pixels, a block 1024; grid-stride beyond 2048 blocks
@@ -885,8 +893,8 @@ static dim3 grid_of_fours(size_t pixels) {   // a lane owns four plane pixels, a
 // member: on the group's front-end queue, behind a pending upload, which is submitted first).
 static int upload_scaled_into(xrhip_klt *c, const FrameSource &s, uint8_t *dst) {
     const int cw = s.geo->crop_width, ch = s.geo->crop_height;
-    ScaleArgs a = scale_args(c, xrh::crop_origin(s.pixels, s.stride, *s.geo, s.pf.bpp), s.stride, s.pf.bpp, upf_word(s.pf), cw, ch, dst);
-    const dim3 grid = grid_of_fours((size_t)c->w * c->h);
+    ScaleArgs a = scale_args(s.pw, s.ph, xrh::crop_origin(s.pixels, s.stride, *s.geo, s.pf.bpp), s.stride, s.pf.bpp, upf_word(s.pf), cw, ch, dst);
+    const dim3 grid = grid_of_fours((size_t)s.pw * s.ph);
     const size_t row = (size_t)cw * s.pf.bpp, bytes = row * ch;
     const uint8_t *staged = nullptr;   // host frame: the slot that holds the crop
     int slot = 0;
@@ -921,8 +929,8 @@ static int upload_bayer_into(xrhip_klt *c, const FrameSource &s, uint8_t *dst) {
     a.src = s.scaled ? xrh::crop_origin(s.pixels, s.stride, *s.geo, pf.bpp) : s.pixels;
     a.sstride = s.stride;
     a.dst = dst;
-    a.w = s.scaled ? s.geo->crop_width : c->w;
-    a.h = s.scaled ? s.geo->crop_height : c->h;
+    a.w = s.scaled ? s.geo->crop_width : s.pw;
+    a.h = s.scaled ? s.geo->crop_height : s.ph;
     a.bpp = pf.bpp;
     a.shift = (int)pf.shift;
     a.px = pf.px;
@@ -934,9 +942,9 @@ static int upload_bayer_into(xrhip_klt *c, const FrameSource &s, uint8_t *dst) {
         if (rc) return rc;
         a.dst = c->bayer_gray;
     }
-    const ScaleArgs sa = scale_args(c, c->bayer_gray, a.w, 1, 0, a.w, a.h, dst);   // (scaled only)
+    const ScaleArgs sa = scale_args(s.pw, s.ph, c->bayer_gray, a.w, 1, 0, a.w, a.h, dst);   // (scaled only)
     const bool scaled = s.scaled;
-    const dim3 grid = grid_of_fours(pixels), scale_grid = grid_of_fours((size_t)c->w * c->h);
+    const dim3 grid = grid_of_fours(pixels), scale_grid = grid_of_fours((size_t)s.pw * s.ph);
     const uint8_t *staged = nullptr;   // host frame: the slot that holds the mosaic
     int slot = 0;
     if (!s.on_device) {
@@ -965,21 +973,50 @@ static int upload_bayer_into(xrhip_klt *c, const FrameSource &s, uint8_t *dst) {
 // Every xrhip_image_upload* entry point (`who`).  distorted: the frame is as the camera recorded it and k_undistort rectifies it into
 // the plane -- reduced / scaled into undist_src first, rectified second: the gray frame takes the place of the one a gray camera of
 // the plane's size would have recorded; such a frame already in HBM is remapped where it lies.
-static int upload_frame(xrhip_image *im, const FrameSource &s, const char *bad_format, bool distorted, const char *who) {
+//
+// Under an orientation (xrhip_klt_set_orientation, o != 0) the same uploads run in the source's orientation -- the plane they write is
+// orient_src, h x w for odd r (s.pw x s.ph); exact area scaling commutes with the eight orientations, so the working-size result is
+// what is turned -- and k_orient turns it into the plane (or undist_src) with a launch of its own in the context's order, like the
+// scaled upload's (a group member: on the group's front-end queue, behind its pending upload, which is submitted first).
+static int upload_frame(xrhip_image *im, const FrameSource &handed, const char *bad_format, bool distorted, const char *who) {
+    FrameSource s = handed;   // (a reference: the callers' bad_format argument fills in handed.pf)
+    const int o = im ? im->ctx->orient : 0;
+    if (im) {
+        s.pw = (o & 1) ? im->ctx->h : im->ctx->w;
+        s.ph = (o & 1) ? im->ctx->w : im->ctx->h;
+    }
     int rc = check_frame(who, im, s, bad_format);
     if (rc) return rc;
     xrhip_klt *c = im->ctx;
     if (distorted && !c->have_undist) return frame_fail(XRHIP_ESTATE, who, "no undistortion map (xrhip_klt_set_undistort_map)");
     const uint8_t *remap_src = c->undist_src;
     int remap_stride = c->w;
-    if (distorted && s.on_device && !s.scaled && !s.pf.bayer && s.pf.bpp == 1 && upf_word(s.pf) == 0) {
+    if (o == 0 && distorted && s.on_device && !s.scaled && !s.pf.bayer && s.pf.bpp == 1 && upf_word(s.pf) == 0) {
         remap_src = s.pixels;
         remap_stride = s.stride;
     } else {
         // (a host buffer may be reused by the caller as soon as we return: PushImage deep-copies, the pinned slot holds our copy)
-        uint8_t *dst = distorted ? c->undist_src : im->raw;
+        uint8_t *plane = distorted ? c->undist_src : im->raw, *dst = plane;
+        if (o != 0) {
+            // (once per context, by its first turned frame, like bayer_gray: hipMalloc may synchronise the device, which a group
+            // member then does in the middle of the group's frame -- a one-off delay, results unchanged; the size never grows)
+            if (!c->orient_src) XR_HIP(hipMalloc(&c->orient_src, ((size_t)c->w * c->h + 3) & ~(size_t)3));
+            dst = c->orient_src;
+        }
         rc = s.pf.bayer ? upload_bayer_into(c, s, dst) : s.scaled ? upload_scaled_into(c, s, dst) : upload_into(c, s, dst);
         if (rc) return rc;
+        if (o != 0) {
+            // in source coordinates: r even: (fx ? w-1-X : X, fy ? h-1-Y : Y); r odd: (fx ? h-1-Y : Y, fy ? w-1-X : X)
+            static const int FX[8] = {0, 0, 1, 1, 1, 1, 0, 0}, FY[8] = {0, 1, 1, 0, 0, 1, 1, 0};
+            const OrientArgs a{c->orient_src, plane, c->w, c->h, o & 1, FX[o], FY[o]};
+            const dim3 grid = a.transpose ? dim3((c->w + OR_T - 1) / OR_T, (c->h + OR_T - 1) / OR_T) : grid_of_fours((size_t)c->w * c->h);
+            rc = klt_run(c, [=](hipStream_t st) {
+                hipLaunchKernelGGL(k_orient, grid, dim3(256), 0, st, a);
+                XR_HIP(hipGetLastError());
+                return XRHIP_OK;
+            });
+            if (rc) return rc;
+        }
     }
     if (distorted) {   // (not batched: a remap per frame on a path the bench's resident / rectified inputs do not take)
         rc = klt_run(c, [=](hipStream_t st) {
@@ -1130,6 +1167,18 @@ int xrhip_image_upload_scaled_distorted(xrhip_image *im, const void *pixels, int
                                         const xrhip_frame_geometry *geo) {
     FrameSource s = frame_source(pixels, stride, on_device, geo, true);
     return upload_frame(im, s, xrh::describe_pixel_format(format, bits, limited, s.pf), true, "xrhip_image_upload_scaled_distorted");
+}
+
+int xrhip_klt_set_orientation(xrhip_klt *c, int orientation) {
+    if (!c) return xr_fail(XRHIP_EINVAL, "xrhip_klt_set_orientation: null context");
+    if (orientation < 0 || orientation > 7) return xr_fail(XRHIP_EINVAL, "xrhip_klt_set_orientation: orientation must be 0..7 (quarter turns clockwise + 4 * mirrored)");
+    c->orient = orientation;   // (host state read by the next upload: nothing in flight depends on it)
+    return XRHIP_OK;
+}
+int xrhip_klt_get_orientation(const xrhip_klt *c, int *orientation) {
+    if (!c || !orientation) return xr_fail(XRHIP_EINVAL, "xrhip_klt_get_orientation: null argument");
+    *orientation = c->orient;
+    return XRHIP_OK;
 }
 
 int xrhip_klt_set_undistort_map(xrhip_klt *c, const uint32_t *map2) {

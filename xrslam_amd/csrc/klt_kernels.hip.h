@@ -1880,6 +1880,98 @@ __global__ __launch_bounds__(256) void k_upload_bayer(BayerArgs a) {
     d_upload_bayer<1>(a);
 }
 
+// ------------------------------------------------------------------------------------- turned and mirrored frames (xrhip_klt_set_orientation)
+// The dense gray plane of a frame in the source's orientation -> the dense w x h plane, for the seven orientations o = r + 4 f other
+// than 0 (xrslam_hip.h has the definition).  In source coordinates the plane pixel (X, Y) is
+//   transpose == 0 (r even; the source is w x h):  (fx ? w-1-X : X,  fy ? h-1-Y : Y)      o = 2: fx fy;  4: fx;  6: fy
+//   transpose == 1 (r odd;  the source is h x w):  (fx ? h-1-Y : Y,  fy ? w-1-X : X)      o = 1: fy;  3: fx;  5: fx fy;  7: neither
+// Both planes are read and written in dwords along their own rows; neither row pitch need be a multiple of 4, so the source dwords are
+// put together by load_dwords_unaligned (every fetched dword holds a byte of the plane) and the plane's aligned dwords that straddle
+// a row end go byte by byte, as in d_upload_reduce.
+struct OrientArgs {
+    const uint8_t *src;   // dense, w x h or (transpose) h x w
+    uint8_t *dst;         // dense w x h
+    int w, h;
+    int transpose, fx, fy;
+};
+// r even.  A lane owns four consecutive plane pixels = one dword store; their four source bytes are consecutive too, in reverse where
+// fx is set: the unaligned source dword at the mirrored position, its bytes reversed.
+__device__ __forceinline__ void d_orient_reverse(const OrientArgs &a) {
+    const uint32_t w = (uint32_t)a.w, h = (uint32_t)a.h, total = w * h;
+    const uint32_t n4 = (total + 3u) >> 2;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n4; i += gridDim.x * 256u) {
+        const uint32_t p0 = i << 2;
+        const uint32_t y = p0 / w, x = p0 - y * w;
+        if (x + 4u <= w) {   // (p0 + 4 <= total follows)
+            const uint32_t sy = a.fy ? h - 1u - y : y, sx = a.fx ? w - 4u - x : x;
+            uint32_t d[2];
+            load_dwords_unaligned<1>(reinterpret_cast<uintptr_t>(a.src + (size_t)sy * w + sx), d);
+            reinterpret_cast<uint32_t *>(a.dst)[i] = a.fx ? __builtin_bswap32(d[0]) : d[0];
+        } else {
+            const uint32_t pe = p0 + 4u < total ? p0 + 4u : total;
+            for (uint32_t p = p0; p < pe; ++p) {
+                const uint32_t py = p / w, px = p - py * w;
+                a.dst[p] = a.src[(size_t)(a.fy ? h - 1u - py : py) * w + (a.fx ? w - 1u - px : px)];
+            }
+        }
+    }
+}
+// r odd.  A workgroup turns the plane's tile [X0, X0 + 64) x [Y0, Y0 + 64) through LDS.  Plane row Y's aligned dwords start at
+// X0 + hp + 4 q, hp = -(Y w + X0) mod 4, q = 0 .. 15 -- the same hp in every tile of the row, so the dwords of neighbouring tiles
+// meet -- and reach up to X0 + 66: the tile in LDS is the source rows of X0 .. X0 + 66, one per X, each 64 bytes = the tile's 16 dwords
+// of Y.  Loading: a lane fetches one unaligned source dword, four Y of one X (bytes reversed where fx is set; the last, partial
+// one of a source row byte by byte); 16 lanes read 64 contiguous bytes of a source row.  Storing: a lane gathers the four X of one Y
+// from four LDS rows and stores one aligned dword; 16 lanes write 64 contiguous bytes of a plane row.  A dword that would cross the
+// row's end (w % 4 != 0) goes byte by byte, and so do the hp bytes before the row's first aligned dword (the first tile's).
+// The gather reads 16 LDS rows four apart at one dword column.  Byte and dword accesses see 32 banks, and no row pitch spreads 16 rows
+// four apart over more than 8 of them, so instead of padding the rows their dwords are permuted: dword c of row R lies at
+// c ^ ((R >> 2) & 15) -- 16 different banks for the gather (the two plane rows of a 32-lane group read the same dwords where
+// w % 4 == 0, and the other half of the banks where w is odd; w % 4 == 2 can leave them two-way), and row parity keeps the loading
+// phase's two rows apart.  This bank behaviour is reasoned from the documented bank mapping ((address / 4) mod 32, 32-lane groups),
+// not measured with a counter; the kernel's time is a launch's (profiles/orientation.md), so nothing observable hangs on it.
+constexpr int OR_T = 64;
+constexpr int OR_ROWS = OR_T + 3;
+__device__ __forceinline__ uint32_t orient_lds_dword(uint32_t row, uint32_t col) { return row * 16u + (col ^ ((row >> 2) & 15u)); }
+__device__ __forceinline__ void d_orient_transpose(const OrientArgs &a) {
+    __shared__ uint32_t tile[OR_ROWS * 16];
+    const uint32_t w = (uint32_t)a.w, h = (uint32_t)a.h, X0 = blockIdx.x * OR_T, Y0 = blockIdx.y * OR_T;
+    for (uint32_t item = threadIdx.x; item < (uint32_t)OR_ROWS * 16u; item += 256u) {
+        const uint32_t xl = item >> 4, g = item & 15u, X = X0 + xl, Y = Y0 + 4u * g;
+        if (X >= w || Y >= h) continue;
+        const uint8_t *row = a.src + (size_t)(a.fy ? w - 1u - X : X) * h;
+        uint32_t v = 0;
+        if (Y + 4u <= h) {
+            uint32_t d[2];
+            load_dwords_unaligned<1>(reinterpret_cast<uintptr_t>(row + (a.fx ? h - 4u - Y : Y)), d);
+            v = a.fx ? __builtin_bswap32(d[0]) : d[0];
+        } else {
+            for (uint32_t m = 0; Y + m < h; ++m) v |= (uint32_t)row[a.fx ? h - 1u - Y - m : Y + m] << (8u * m);
+        }
+        tile[orient_lds_dword(xl, g)] = v;
+    }
+    __syncthreads();
+    const uint8_t *tb = reinterpret_cast<const uint8_t *>(tile);
+    for (uint32_t item = threadIdx.x; item < (uint32_t)OR_T * 16u; item += 256u) {
+        const uint32_t yl = item >> 4, q = item & 15u, Y = Y0 + yl;
+        if (Y >= h) continue;
+        const uint32_t rowbase = Y * w, hp = (0u - (rowbase + X0)) & 3u;
+        const uint32_t xl = hp + 4u * q, X = X0 + xl;
+        const auto px = [&](uint32_t r) -> uint32_t { return tb[(orient_lds_dword(r, yl >> 2) << 2) + (yl & 3u)]; };
+        if (X + 4u <= w) {
+            reinterpret_cast<uint32_t *>(a.dst)[(rowbase + X) >> 2] = px(xl) | (px(xl + 1u) << 8) | (px(xl + 2u) << 16) | (px(xl + 3u) << 24);
+        } else {
+            for (uint32_t k = 0; X + k < w; ++k) a.dst[rowbase + X + k] = (uint8_t)px(xl + k);   // (at most three)
+        }
+        if (X0 == 0u && q == 0u)
+            for (uint32_t k = 0; k < hp && k < w; ++k) a.dst[rowbase + k] = (uint8_t)px(k);
+    }
+}
+// grid: transpose ? (ceil(w / OR_T), ceil(h / OR_T)) : grid_of_fours(w * h)
+__global__ __launch_bounds__(256) void k_orient(OrientArgs a) {
+    if (a.transpose) return d_orient_transpose(a);
+    d_orient_reverse(a);
+}
+
 // ---------------------------------------------------------------------------------------------- tracking view (xrhip_image_render_view)
 // Line segments and discs over a frame's gray plane, all in integers.  Which primitive a pixel shows must not depend on how the GPU
 // schedules the lanes: k_view_stamp takes atomicMax of a word ordered like the priority rule into a 32-bit owner plane (cleared per

@@ -8,10 +8,14 @@
 //   xrslam-player --slam configs/euroc_slam.yaml --device configs/euroc_sensor.yaml --euroc <dir>/mav0
 //                 [--out traj.tum] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined]
 //                 [--push-color] [--push-format gray16|rgb|rgba|bayer_rggb8|bayer_bggr16] [--push-scaled] [--cov-out FILE]
+//                 [--push-oriented rot90|rot180|rot270|flip|flip-rot90|flip-rot180|flip-rot270|0..7]
 //
 // (--push-color: a colour PNG is pushed as BGR / BGRA with channel 3 / 4 and reduced to gray by the library instead of by the reader.)
 // (--push-scaled: a PNG larger than cam0.resolution is pushed at its own size, the whole frame as the crop, and cropped / area-scaled
 // down by the library -- through any --push-color / --push-format setting; without the flag a size mismatch is an error.)
+// (--push-oriented O: every PNG is turned by the inverse of orientation O in the reader -- the frame a sensor mounted that way would
+// deliver -- and XRSLAMAmdSetFrameOrientation(O) has the library turn it back in the frame's upload: the run sees the original images.
+// Works through --push-color / --push-format / --push-scaled; the reader's own rectification (--host-undistort) takes upright frames.)
 // (--push-format: a 16-bit PNG is handed to the library as GRAY16 instead of being stripped to its high byte by the reader; a colour
 // PNG as RGB8 / RGBA8 -- XRSLAMAmdPushImageFormat.  bayer_rggb8 / bayer_bggr16: the gray PNG becomes a raw mosaic whose every site
 // holds the gray value -- bytes, or 16-bit samples with the value in the high byte -- and is pushed as BAYER_RGGB8 / BAYER_BGGR16.)
@@ -45,6 +49,34 @@
 
 using namespace xrplayer;
 
+// --push-oriented: a name or 0..7 -> the orientation o = quarter turns clockwise + 4 * mirrored first, -1 if it is neither
+static int parse_orientation(const std::string &s) {
+    static const char *names[8] = {"none", "rot90", "rot180", "rot270", "flip", "flip-rot90", "flip-rot180", "flip-rot270"};
+    for (int o = 0; o < 8; ++o)
+        if (s == names[o]) return o;
+    if (s == "transverse") return 5;
+    if (s == "flipv") return 6;
+    if (s == "transpose") return 7;
+    return s.size() == 1 && s[0] >= '0' && s[0] <= '7' ? s[0] - '0' : -1;
+}
+// The image whose turn by orientation o is `img`: its turn by the inverse orientation (a mirrored orientation undoes itself, a plain
+// turn is undone by the opposite turn), pixel by pixel whatever a pixel's bytes are
+static void turn_back(GrayImage &img, int o) {
+    const int inv = (o & 4) ? o : (4 - o) & 3;
+    if (inv == 0) return;
+    const int W = (inv & 1) ? img.h : img.w, H = (inv & 1) ? img.w : img.h, c = img.channels;
+    std::vector<uint8_t> out(img.px.size());
+    for (int j = 0; j < img.h; ++j)
+        for (int i = 0; i < img.w; ++i) {
+            long long X, Y;
+            xrh::orient_point(inv, img.w, img.h, i, j, X, Y);
+            std::memcpy(&out[((size_t)Y * W + (size_t)X) * c], &img.px[((size_t)j * img.w + i) * c], (size_t)c);
+        }
+    img.px.swap(out);
+    img.w = W;
+    img.h = H;
+}
+
 static const TruthRow *nearest_truth(const std::vector<TruthRow> &gt, double t, double tol) {
     if (gt.empty()) return nullptr;
     size_t lo = 0, hi = gt.size();
@@ -63,6 +95,7 @@ int main(int argc, char **argv) {
     bool undistort = true, host_undistort = false, pipelined = false, push_color = false, push_scaled = false;
     int png_keep = PNG_GRAY;   // --push-format
     int push_bayer = -1;       // --push-format bayer_*: the XRSLAMAmdPixelFormat the gray frames are pushed as
+    int push_oriented = 0;     // --push-oriented: the orientation the frames are pushed in
     // the reference's option names (main.cpp:57-71) map onto ours
     const std::map<std::string, std::string> alias = {{"-sc", "slam"}, {"--slamconfig", "slam"}, {"-dc", "device"},
                                                       {"--deviceconfig", "device"}, {"-lc", "license"}, {"--license", "license"},
@@ -74,6 +107,13 @@ int main(int argc, char **argv) {
         else if (a == "--pipelined") pipelined = true;
         else if (a == "--push-color") push_color = true;   // colour PNGs are pushed as BGR / BGRA (channel 3 / 4): the library reduces them
         else if (a == "--push-scaled") push_scaled = true;   // PNGs larger than cam0.resolution are scaled down by the library
+        else if (a == "--push-oriented" && i + 1 < argc) {
+            push_oriented = parse_orientation(argv[++i]);
+            if (push_oriented < 0) {
+                std::fprintf(stderr, "--push-oriented: rot90, rot180, rot270, flip, flip-rot90, flip-rot180, flip-rot270 or 0..7\n");
+                return 2;
+            }
+        }
         else if (a == "--push-format" && i + 1 < argc) {
             const std::string f = argv[++i];
             if (f == "gray16") png_keep = PNG_KEEP_GRAY16;
@@ -107,7 +147,7 @@ int main(int argc, char **argv) {
     }
     if (!opt.count("slam") || !opt.count("device") || !opt.count("euroc")) {
         std::fprintf(stderr, "usage: xrslam-player --slam cfg.yaml --device sensor.yaml --euroc <dir>/mav0 [--out traj.tum] "
-                             "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color] [--push-format gray16|rgb|rgba|bayer_rggb8|bayer_bggr16] [--push-scaled] [--mask mask.pgm|mask.png]\n"
+                             "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color] [--push-format gray16|rgb|rgba|bayer_rggb8|bayer_bggr16] [--push-scaled] [--push-oriented rot90|rot180|rot270|flip|...|0..7] [--mask mask.pgm|mask.png]\n"
                              "       [--cov-out FILE] [--view-out DIR [--view-every N] [--view-mode reference|age] [--view-trail K]]\n"
                              "   or: xrslam-player -sc cfg.yaml -dc sensor.yaml [--tum traj.tum] [--csv traj.csv] [-p] "
                              "euroc://<dir>/mav0 | tum://<dir>/mav0\n");
@@ -155,6 +195,13 @@ int main(int argc, char **argv) {
     const bool device_undistort = undistort && cfg.cam_distortion_flag && !host_undistort;
     if (device_undistort) XRSLAMAmdSetDeviceUndistort(model.c_str());
     if (pipelined) XRSLAMAmdSetThreading(1);
+    if (push_oriented != 0 && XRSLAMAmdSetFrameOrientation(push_oriented) != 1) {
+        std::fprintf(stderr, "--push-oriented: %s\n", XRSLAMAmdLastError());
+        XRSLAMDestroy();
+        return 1;
+    }
+    // the frame as it is pushed: height x width of the working image for odd quarter turns
+    const int frame_w = (int)cfg.cam_resolution[(push_oriented & 1) ? 1 : 0], frame_h = (int)cfg.cam_resolution[(push_oriented & 1) ? 0 : 1];
     if (!mask.px.empty() && XRSLAMAmdSetMask(mask.px.data(), mask.w, 0) != 1) {
         std::fprintf(stderr, "--mask %s: %s\n", opt["mask"].c_str(), XRSLAMAmdLastError());
         XRSLAMDestroy();
@@ -258,8 +305,15 @@ int main(int argc, char **argv) {
             }
             // the library copies cam0.resolution rows x columns out of the buffer it is handed
             // (XRSLAMManager.cpp:113-131 does the same with the configured size): a frame of any other size is an error
-            const bool oversized = push_scaled && img.w >= (int)cfg.cam_resolution[0] && img.h >= (int)cfg.cam_resolution[1] &&
-                                   (img.w != (int)cfg.cam_resolution[0] || img.h != (int)cfg.cam_resolution[1]);
+            if (push_oriented != 0) {
+                if (undistort && cfg.cam_distortion_flag && !device_undistort) {
+                    std::fprintf(stderr, "%s: --push-oriented with --host-undistort: the reader rectifies upright frames only\n",
+                                 cam[ev.index].filename.c_str());
+                    break;
+                }
+                turn_back(img, push_oriented);
+            }
+            const bool oversized = push_scaled && img.w >= frame_w && img.h >= frame_h && (img.w != frame_w || img.h != frame_h);
             if (oversized) {   // --push-scaled: the frame goes in at its own size, the whole of it as the crop
                 if (undistort && cfg.cam_distortion_flag && !device_undistort) {
                     std::fprintf(stderr, "%s: --push-scaled with --host-undistort: the reader rectifies working-size frames only\n",
@@ -272,9 +326,9 @@ int main(int argc, char **argv) {
                                               : img.channels == 4 ? (int)XRSLAM_AMD_PIXEL_BGRA8 : (int)XRSLAM_AMD_PIXEL_GRAY8, 0, 0};
                 const XRSLAMAmdFrameGeometry geo{img.w, img.h, 0, 0, img.w, img.h};
                 XRSLAMAmdPushImageScaled(img.px.data(), img.w * img.channels, &ff, &geo, 0, ev.t);
-            } else if (img.w != (int)cfg.cam_resolution[0] || img.h != (int)cfg.cam_resolution[1]) {
+            } else if (img.w != frame_w || img.h != frame_h) {
                 std::fprintf(stderr, "%s: image is %dx%d, the device configuration says %dx%d\n", cam[ev.index].filename.c_str(), img.w,
-                             img.h, (int)cfg.cam_resolution[0], (int)cfg.cam_resolution[1]);
+                             img.h, frame_w, frame_h);
                 break;
             }
             const bool rectify_here = !oversized && undistort && cfg.cam_distortion_flag && !device_undistort;

@@ -131,6 +131,12 @@ def load(lib_path):
         lib.XRSLAMAmdPushImageScaled.restype = None
         lib.XRSLAMAmdScaleIntrinsics.argtypes = [C.c_void_p, C.POINTER(XRSLAMAmdFrameGeometry), C.c_int, C.c_int, C.c_void_p]
         lib.XRSLAMAmdScaleIntrinsics.restype = None
+    have_orient = hasattr(lib, "XRSLAMAmdSetFrameOrientation")
+    if have_orient:   # turned / mirrored frames
+        lib.XRSLAMAmdSetFrameOrientation.argtypes = [C.c_int]
+        lib.XRSLAMAmdGetFrameOrientation.argtypes = []
+        lib.XRSLAMAmdOrientationFromExif.argtypes = [C.c_int]
+        lib.XRSLAMAmdOrientIntrinsics.argtypes = [C.c_void_p, C.POINTER(XRSLAMAmdFrameGeometry), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.XRSLAMAmdGetTimes.argtypes = [C.POINTER(XRSLAMAmdTimes)]
     lib.XRSLAMAmdGetTimes.restype = None
     lib.XRSLAMAmdLastError.restype = C.c_char_p
@@ -184,6 +190,9 @@ def load(lib_path):
             lib.XRSLAMAmdInstanceSetCovariance.restype = None
             lib.XRSLAMAmdInstanceGetCovariance.argtypes = [H, C.POINTER(XRSLAMAmdCovariance)]
             lib.XRSLAMAmdInstanceGetLandmarkVariances.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int]
+        if have_orient:
+            lib.XRSLAMAmdInstanceSetFrameOrientation.argtypes = [H, C.c_int]
+            lib.XRSLAMAmdInstanceGetFrameOrientation.argtypes = [H]
         if have_mask:
             lib.XRSLAMAmdInstanceSetMask.argtypes = [H, C.c_void_p, C.c_int, C.c_int]
             lib.XRSLAMAmdInstanceSetNextFrameMask.argtypes = [H, C.c_void_p, C.c_int, C.c_int]
@@ -280,6 +289,9 @@ class _Api:
             names["push_image_format"] = ("XRSLAMAmdPushImageFormat", "XRSLAMAmdInstancePushImageFormat")
         if hasattr(lib, "XRSLAMAmdPushImageScaled"):
             names["push_image_scaled"] = ("XRSLAMAmdPushImageScaled", "XRSLAMAmdInstancePushImageScaled")
+        if hasattr(lib, "XRSLAMAmdSetFrameOrientation"):
+            names["set_frame_orientation"] = ("XRSLAMAmdSetFrameOrientation", "XRSLAMAmdInstanceSetFrameOrientation")
+            names["get_frame_orientation"] = ("XRSLAMAmdGetFrameOrientation", "XRSLAMAmdInstanceGetFrameOrientation")
         if hasattr(lib, "XRSLAMAmdGetCovariance"):
             names["set_covariance"] = ("XRSLAMAmdSetCovariance", "XRSLAMAmdInstanceSetCovariance")
             names["get_covariance"] = ("XRSLAMAmdGetCovariance", "XRSLAMAmdInstanceGetCovariance")
@@ -295,6 +307,21 @@ class _Api:
             setattr(self, attr, getattr(lib, glob) if handle is None else functools.partial(getattr(lib, inst), handle))
 
 
+def turn_frames(frames, o):
+    """Frames [n][h][w] or [n][h][w][bytes per pixel] turned by orientation o = quarter turns clockwise + 4 * mirrored left to right
+    first (include/XRSLAM.h: XRSLAMAmdSetFrameOrientation): [n][w][h]... for odd quarter turns, contiguous."""
+    o = int(o)
+    if not 0 <= o <= 7:
+        raise ValueError("orientation %d is not 0..7" % o)
+    f = frames[:, :, ::-1] if o >> 2 else frames
+    return np.ascontiguousarray(np.rot90(f, -(o & 3), axes=(1, 2)))
+
+
+def inverse_orientation(o):
+    """The orientation that undoes o: a mirrored one undoes itself, a plain turn is undone by the opposite turn"""
+    return int(o) if int(o) >> 2 else (4 - int(o)) & 3
+
+
 class Session:
     """One XRSLAM instance: the process singleton behind the reference's six symbols (XRSLAMManager.cpp:6-9), or --
     instance=True -- an XRSLAMAmdInstance of its own, so that several sessions can live in one process.
@@ -302,12 +329,18 @@ class Session:
     pixel_format (see frame_format): the frames are rows of bytes in that layout, [n][h][row bytes] (or [n][h][w][bytes per pixel]),
     pushed through XRSLAMAmdPushImageFormat / XRSLAMAmdInstanceReplayFormat from host memory or from device_frames.
     geometry (see frame_geometry): the frames are larger than cam0.resolution and go through XRSLAMAmdPushImageScaled /
-    XRSLAMAmdInstanceReplayScaled, in pixel_format (None: GRAY8)."""
+    XRSLAMAmdInstanceReplayScaled, in pixel_format (None: GRAY8).
+    orientation (0..7): every host frame of seq is turned by the INVERSE orientation here, as a camera mounted that way would deliver it,
+    and XRSLAMAmdSetFrameOrientation(orientation) has the library turn it back in its upload: the run sees the original images.
+    (device_frames are taken as they are: the caller stages them already turned, e.g. with turn_frames / inverse_orientation.)"""
 
     def __init__(self, lib_path, seq, slam_yaml=SLAM_YAML, sensor_yaml=SENSOR_YAML, device_frames=None,
                  init_frames=60, instance=False, device_undistort=None, threading=0, group=None, channels=1, pixel_format=None,
-                 geometry=None):
+                 geometry=None, orientation=0):
         self.lib = load(lib_path)
+        self.orientation = int(orientation)
+        if self.orientation and device_frames is None:
+            seq = dict(seq, frames=turn_frames(np.asarray(seq["frames"]), inverse_orientation(self.orientation)))
         self.channels = int(channels)
         self.pixel_format = None if pixel_format is None else frame_format(pixel_format)
         self.geometry = None if geometry is None else frame_geometry(geometry)
@@ -327,6 +360,8 @@ class Session:
             if ok != 1:
                 raise RuntimeError("XRSLAMCreate failed: %s" % self.lib.XRSLAMAmdLastError().decode())
             self.api = _Api(self.lib)
+        if self.orientation:
+            self.set_frame_orientation(self.orientation)
         if threading:   # 1 = backend of frame t beside the feature tracker of frame t+1 (XRSLAMAmdSetThreading)
             self.api.set_threading(int(threading))
         if device_undistort:   # frames are pushed as the camera recorded them and rectified on the GPU
@@ -435,6 +470,11 @@ class Session:
         for r in out[:k]:
             self.poses.append([r[0]] + list(r[1:4]) + list(r[4:8]))
         return k
+
+    def set_frame_orientation(self, o):
+        """XRSLAMAmdSetFrameOrientation: the frames pushed from now on are turned like that (the caller supplies them so)"""
+        if self.api.set_frame_orientation(int(o)) != 1:
+            raise RuntimeError("XRSLAMAmdSetFrameOrientation: %s" % self.error())
 
     def flush(self):
         """Pushes the IMU samples after the last frame so the last queued frame is processed

@@ -7,7 +7,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .abi import FrameGeometry, mask_args
+from .abi import FrameGeometry, mask_args, orientation
 
 
 class KltStats(C.Structure):
@@ -71,6 +71,9 @@ def _bind():
     L.xrhip_klt_set_mask.argtypes = [vp, vp, C.c_int, C.c_int]
     L.xrhip_image_set_mask.argtypes = [vp, vp, C.c_int, C.c_int]
     L.xrhip_debug_get_mask.argtypes = [vp, vp]
+    if hasattr(L, "xrhip_klt_set_orientation"):   # (XRSLAM_HIP_LIB may name an earlier build's library: tools/orientation.py)
+        L.xrhip_klt_set_orientation.argtypes = [vp, C.c_int]
+        L.xrhip_klt_get_orientation.argtypes = [vp, C.POINTER(C.c_int)]
     return L
 
 
@@ -164,6 +167,23 @@ class KltContext:
         ptr, stride = mask_args(mask, self.w, self.h, on_device, stride)
         check(L().xrhip_klt_set_mask(self._h, ptr, stride, 1 if on_device else 0))
 
+    def set_orientation(self, o):
+        """Frames arrive turned or mirrored (include/xrslam_hip.h, xrhip_klt_set_orientation): o = quarter turns clockwise + 4 * mirrored
+        first, 0..7 or a name of xrslam_amd.abi.ORIENT_NAMES.  Sticky, from the next upload on: an unscaled frame is then [w][h] for odd
+        quarter turns, and the upload turns it into the plane."""
+        check(L().xrhip_klt_set_orientation(self._h, orientation(o)))
+
+    def get_orientation(self):
+        if not hasattr(L(), "xrhip_klt_get_orientation"):
+            return 0
+        o = C.c_int(0)
+        check(L().xrhip_klt_get_orientation(self._h, C.byref(o)))
+        return o.value
+
+    def frame_size(self):
+        """(width, height) of an unscaled frame as the uploads read it under the current orientation"""
+        return (self.h, self.w) if self.get_orientation() & 1 else (self.w, self.h)
+
     def set_undistort_map(self, map2):
         """Packed 1/32-pixel inverse map [h][w][2] uint32 (include/xrslam_hip.h), or None to switch the device
         undistortion off."""
@@ -209,13 +229,13 @@ class HipImage:
 
     def upload(self, gray):
         gray = np.ascontiguousarray(gray, dtype=np.uint8)
-        assert gray.shape == (self.ctx.h, self.ctx.w), gray.shape
+        assert gray.shape == self.ctx.frame_size()[::-1], gray.shape
         check(L().xrhip_image_upload(self._h, _p(gray), gray.strides[0]))
 
     def upload_distorted(self, gray):
         """The frame as the camera recorded it: rectified on the device (KltContext.set_undistort_map)."""
         gray = np.ascontiguousarray(gray, dtype=np.uint8)
-        assert gray.shape == (self.ctx.h, self.ctx.w), gray.shape
+        assert gray.shape == self.ctx.frame_size()[::-1], gray.shape
         check(L().xrhip_image_upload_distorted(self._h, _p(gray), gray.strides[0], 0))
 
     def upload_distorted_device(self, dev_ptr, stride):
@@ -227,8 +247,9 @@ class HipImage:
         per pixel] (interleaved: the latter, as wide as the plane); rows may be padded, pixels not."""
         if on_device:
             return C.c_void_p(int(pixels)), int(stride)
-        assert pixels.dtype == np.uint8 and pixels.ndim in (2, 3) and pixels.shape[0] == (rows or self.ctx.h), pixels.shape
-        assert not interleaved or (pixels.ndim == 3 and pixels.shape[1] == self.ctx.w), pixels.shape
+        fw, fh = self.ctx.frame_size()
+        assert pixels.dtype == np.uint8 and pixels.ndim in (2, 3) and pixels.shape[0] == (rows or fh), pixels.shape
+        assert not interleaved or (pixels.ndim == 3 and pixels.shape[1] == fw), pixels.shape
         assert pixels.strides[-1] == 1 and (pixels.ndim == 2 or pixels.strides[1] == pixels.shape[2]), pixels.strides
         return _p(pixels), pixels.strides[0]
 
