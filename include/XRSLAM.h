@@ -169,8 +169,16 @@ void XRSLAMAmdPushImageDeviceColor(const void *pixels_dev, int stride, int chann
  *                   ROS bayer_* convention; OpenCV's COLOR_Bayer* names are shifted by one pixel against it).  Demosaiced bilinearly,
  *                   neighbours mirrored at the frame's (a scaled frame: the crop's) edges, and weighted like BGR8, in exact integer
  *                   arithmetic with one rounding (include/xrslam_hip.h has the formula); a constant mosaic gives that constant
+ *   GRAY10_MIPI / GRAY12_MIPI / GRAY10P / GRAY12P and BAYER_<pattern>{10_MIPI, 12_MIPI, 10P, 12P}
+ *                   bit-packed 10 / 12-bit samples as sensors send them: CSI-2 RAW10 / RAW12 (4 pixels in 5 bytes / 2 in 3, the low
+ *                   bits in the group's last byte; V4L2 Y10P, Y12P, pRAA, pRCC ...) and the PFNC lsb-packed forms (Mono10p,
+ *                   Mono12p, BayerRG10p ...: the row is one little-endian bit stream).  `stride` >= the packed row's bytes
+ *                   (5 * ceil(w/4), 3 * ceil(w/2), ceil(10w/8), ceil(12w/8)); `bits` is not read.  The result is, bit for bit, that of
+ *                   the same samples pushed as GRAY16 / BAYER_<pattern>16 with bits 10 / 12 (include/xrslam_hip.h has the byte
+ *                   layouts).  Not supported: GigE Vision's legacy Mono10Packed / Mono12Packed, msb-packed or big-endian PFNC
+ *                   forms, 14-bit packings
  * limited_range (video levels, luma 16..235; not for the RGB / BGR and Bayer formats): gray' = min(255, ((max(gray,16) - 16) * 255 + 109) / 219).
- * Any base alignment, any stride >= width * bytes per pixel.  With device undistortion on: reduced first, rectified second.  A bad
+ * Any base alignment, any stride >= width * bytes per pixel (the packed forms: the row's bytes).  With device undistortion on: reduced first, rectified second.  A bad
  * format, bits, stride or flag drops the frame and sets XRSLAMAmdLastError; nothing aborts. */
 typedef enum XRSLAMAmdPixelFormat {
     XRSLAM_AMD_PIXEL_GRAY8 = 0,
@@ -192,11 +200,33 @@ typedef enum XRSLAMAmdPixelFormat {
     XRSLAM_AMD_PIXEL_BAYER_RGGB16 = 20,
     XRSLAM_AMD_PIXEL_BAYER_GRBG16 = 21,
     XRSLAM_AMD_PIXEL_BAYER_GBRG16 = 22,
-    XRSLAM_AMD_PIXEL_BAYER_BGGR16 = 23
+    XRSLAM_AMD_PIXEL_BAYER_BGGR16 = 23,
+    /* (24..31 are not formats) */
+    XRSLAM_AMD_PIXEL_GRAY10_MIPI = 32,
+    XRSLAM_AMD_PIXEL_GRAY12_MIPI = 33,
+    XRSLAM_AMD_PIXEL_GRAY10P = 34,
+    XRSLAM_AMD_PIXEL_GRAY12P = 35,
+    /* (36..39 are not formats)  BAYER_<pattern><packing> = 40 + 4 * packing + pattern */
+    XRSLAM_AMD_PIXEL_BAYER_RGGB10_MIPI = 40,
+    XRSLAM_AMD_PIXEL_BAYER_GRBG10_MIPI = 41,
+    XRSLAM_AMD_PIXEL_BAYER_GBRG10_MIPI = 42,
+    XRSLAM_AMD_PIXEL_BAYER_BGGR10_MIPI = 43,
+    XRSLAM_AMD_PIXEL_BAYER_RGGB12_MIPI = 44,
+    XRSLAM_AMD_PIXEL_BAYER_GRBG12_MIPI = 45,
+    XRSLAM_AMD_PIXEL_BAYER_GBRG12_MIPI = 46,
+    XRSLAM_AMD_PIXEL_BAYER_BGGR12_MIPI = 47,
+    XRSLAM_AMD_PIXEL_BAYER_RGGB10P = 48,
+    XRSLAM_AMD_PIXEL_BAYER_GRBG10P = 49,
+    XRSLAM_AMD_PIXEL_BAYER_GBRG10P = 50,
+    XRSLAM_AMD_PIXEL_BAYER_BGGR10P = 51,
+    XRSLAM_AMD_PIXEL_BAYER_RGGB12P = 52,
+    XRSLAM_AMD_PIXEL_BAYER_GRBG12P = 53,
+    XRSLAM_AMD_PIXEL_BAYER_GBRG12P = 54,
+    XRSLAM_AMD_PIXEL_BAYER_BGGR12P = 55
 } XRSLAMAmdPixelFormat;
 typedef struct XRSLAMAmdFrameFormat {
     int format;          /* XRSLAMAmdPixelFormat */
-    int bits;            /* GRAY16, BAYER_*16: significant bits, 8..16; 0 = 16.  Not read for the other formats. */
+    int bits;            /* GRAY16, BAYER_*16: significant bits, 8..16; 0 = 16.  Not read for the other formats (the packed ones carry theirs). */
     int limited_range;   /* 1: video levels, expanded to 0..255 */
 } XRSLAMAmdFrameFormat;
 void XRSLAMAmdPushImageFormat(const void *pixels, int stride, const XRSLAMAmdFrameFormat *fmt, int on_device, double timestamp);

@@ -134,7 +134,27 @@ int xrhip_image_upload_color_distorted(xrhip_image *img, const void *pixels, int
  * behind its pending shared upload, like the scaled upload); a host frame goes through the pinned slots to an HBM scratch, a frame in
  * HBM is read where it lies.  xrhip_image_upload_scaled*: the crop is a Bayer frame of its own -- its phase is the source's shifted by
  * (crop_x & 1, crop_y & 1), neighbours mirror at the crop's edges, only the crop's bytes are read -- and g(i, j) of the area mean is the
- * Bayer gray of crop pixel (i, j).  Format numbers 11..15 and 24.. are not formats. */
+ * Bayer gray of crop pixel (i, j).
+ *
+ * Packed 10 / 12-bit samples (CSI-2 sensors: MIPI RAW10 / RAW12, V4L2 Y10P / Y12P / pRAA / pRCC; GigE Vision and USB3 Vision: the
+ * PFNC lsb-packed Mono10p / Mono12p / BayerRG10p ...), unpacked as part of the upload.  A row is a run of bit-packed samples; row y
+ * starts at pixels + y * stride_bytes, any base alignment, any stride_bytes >= the row's bytes.  B[k]: byte k of the row, v(x): the
+ * sample of pixel x:
+ *   *10_MIPI   4 px in 5 bytes, g = x >> 2, i = x & 3    v = B[5g+i] << 2 | ((B[5g+4] >> 2i) & 3)     5 * ceil(width / 4) bytes a row
+ *   *12_MIPI   2 px in 3 bytes, g = x >> 1, i = x & 1    v = B[3g+i] << 4 | ((B[3g+2] >> 4i) & 15)    3 * ceil(width / 2)
+ *   *10P       the row is one little-endian bit stream   v = its bits [10x, 10x + 10)                 ceil(10 * width / 8)
+ *   *12P       the same                                  v = its bits [12x, 12x + 12)                 ceil(12 * width / 8)
+ * A MIPI row holds whole groups; any width >= 1 (Bayer: >= 2).  A packed frame gives, bit for bit, the plane of the same samples
+ * written as little-endian 16-bit values and uploaded as GRAY16 (GRAY10_MIPI .. GRAY12P) or BAYER_<pattern>16 with bits = 10 / 12 --
+ * through limited_range (the mono forms; XRHIP_EINVAL for the Bayer forms), crop and area scale (a Bayer crop's phase shifts with its
+ * origin, as above), orientation, undistortion and masks.  `bits` is not read.  (min(255, v >> (bits - 8)) of such a sample is its top
+ * 8 bits: the MIPI forms' gray value never needs the group's low-bits byte.)  One launch of k_upload_packed in the context's order for
+ * a mono frame of the plane's size; a mosaic or a scaled frame is unpacked to an HBM scratch of 8-bit samples and the Bayer / scaled
+ * upload's kernels run on that (2 launches; a scaled mosaic 3).  A host frame goes through the pinned slots as it is packed (1.25 / 1.5
+ * bytes a pixel; of a scaled one only the byte groups that hold a crop pixel).  Not supported: GigE Vision's legacy Mono10Packed /
+ * Mono12Packed (another nibble order), big-endian or msb-packed PFNC forms, 14-bit packings; a group member's packed frame is not
+ * part of the group's shared upload launch (a launch of its own behind it, like a Bayer frame).
+ * Format numbers 11..15, 24..31, 36..39 and 56.. are not formats. */
 #define XRHIP_PIXFMT_GRAY8 0
 #define XRHIP_PIXFMT_BGR8 1
 #define XRHIP_PIXFMT_BGRA8 2
@@ -154,6 +174,27 @@ int xrhip_image_upload_color_distorted(xrhip_image *img, const void *pixels, int
 #define XRHIP_PIXFMT_BAYER_GRBG16 21
 #define XRHIP_PIXFMT_BAYER_GBRG16 22
 #define XRHIP_PIXFMT_BAYER_BGGR16 23
+#define XRHIP_PIXFMT_GRAY10_MIPI 32
+#define XRHIP_PIXFMT_GRAY12_MIPI 33
+#define XRHIP_PIXFMT_GRAY10P 34
+#define XRHIP_PIXFMT_GRAY12P 35
+/* BAYER_<pattern><packing> = 40 + 4 * packing + pattern */
+#define XRHIP_PIXFMT_BAYER_RGGB10_MIPI 40
+#define XRHIP_PIXFMT_BAYER_GRBG10_MIPI 41
+#define XRHIP_PIXFMT_BAYER_GBRG10_MIPI 42
+#define XRHIP_PIXFMT_BAYER_BGGR10_MIPI 43
+#define XRHIP_PIXFMT_BAYER_RGGB12_MIPI 44
+#define XRHIP_PIXFMT_BAYER_GRBG12_MIPI 45
+#define XRHIP_PIXFMT_BAYER_GBRG12_MIPI 46
+#define XRHIP_PIXFMT_BAYER_BGGR12_MIPI 47
+#define XRHIP_PIXFMT_BAYER_RGGB10P 48
+#define XRHIP_PIXFMT_BAYER_GRBG10P 49
+#define XRHIP_PIXFMT_BAYER_GBRG10P 50
+#define XRHIP_PIXFMT_BAYER_BGGR10P 51
+#define XRHIP_PIXFMT_BAYER_RGGB12P 52
+#define XRHIP_PIXFMT_BAYER_GRBG12P 53
+#define XRHIP_PIXFMT_BAYER_GBRG12P 54
+#define XRHIP_PIXFMT_BAYER_BGGR12P 55
 int xrhip_image_upload_format(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits, int limited_range,
                               int on_device);
 int xrhip_image_upload_format_distorted(xrhip_image *img, const void *pixels, int stride_bytes, int format, int bits,

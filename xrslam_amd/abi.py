@@ -184,6 +184,25 @@ PIXFMT_BYTES = {PIXFMT_GRAY8: 1, PIXFMT_BGR8: 3, PIXFMT_BGRA8: 4, PIXFMT_RGB8: 3
 PIXFMT_BAYER_RGGB8, PIXFMT_BAYER_GRBG8, PIXFMT_BAYER_GBRG8, PIXFMT_BAYER_BGGR8, PIXFMT_BAYER_RGGB16, PIXFMT_BAYER_GRBG16, \
     PIXFMT_BAYER_GBRG16, PIXFMT_BAYER_BGGR16 = range(16, 24)
 PIXFMT_BAYER_BYTES = {f: 1 if f < PIXFMT_BAYER_RGGB16 else 2 for f in range(16, 24)}
+# Packed 10 / 12-bit samples (24..31, 36..39 and 56.. are not formats).  Packings in format-number order: CSI-2 RAW10 / RAW12 groups,
+# then the PFNC lsb-packed bit streams; GRAY = 32 + packing, BAYER = 40 + 4 * packing + pattern (the patterns in the order above)
+PACKINGS = (("mipi", 10), ("mipi", 12), ("lsb", 10), ("lsb", 12))
+PIXFMT_GRAY10_MIPI, PIXFMT_GRAY12_MIPI, PIXFMT_GRAY10P, PIXFMT_GRAY12P = range(32, 36)
+PIXFMT_BAYER_RGGB10_MIPI, PIXFMT_BAYER_GRBG10_MIPI, PIXFMT_BAYER_GBRG10_MIPI, PIXFMT_BAYER_BGGR10_MIPI, \
+    PIXFMT_BAYER_RGGB12_MIPI, PIXFMT_BAYER_GRBG12_MIPI, PIXFMT_BAYER_GBRG12_MIPI, PIXFMT_BAYER_BGGR12_MIPI, \
+    PIXFMT_BAYER_RGGB10P, PIXFMT_BAYER_GRBG10P, PIXFMT_BAYER_GBRG10P, PIXFMT_BAYER_BGGR10P, \
+    PIXFMT_BAYER_RGGB12P, PIXFMT_BAYER_GRBG12P, PIXFMT_BAYER_GBRG12P, PIXFMT_BAYER_BGGR12P = range(40, 56)
+# format -> (packing, bits, Bayer phase (px, py) of RGGB or None for the mono forms)
+PIXFMT_PACKED = {32 + p: PACKINGS[p] + (None,) for p in range(4)}
+PIXFMT_PACKED.update({40 + 4 * p + k: PACKINGS[p] + ((k & 1, k >> 1),) for p in range(4) for k in range(4)})
+
+
+def packed_row_bytes(fmt, width):
+    """bytes that hold a row of `width` pixels of the packed format `fmt`"""
+    packing, bits, _ = PIXFMT_PACKED[fmt]
+    if packing == "mipi":
+        return (5 * ((width + 3) // 4)) if bits == 10 else (3 * ((width + 1) // 2))
+    return (bits * width + 7) // 8
 
 
 class FrameGeometry(C.Structure):

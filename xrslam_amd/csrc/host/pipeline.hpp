@@ -434,22 +434,24 @@ struct Pipeline {
         }
         if (in.geo) {
             if (!in.pixels) throw std::runtime_error("Image geometry is not supported: null pixels");
-            if (const char *why = check_frame_geometry(in.geo, fcols, frows, pf.bpp, in.stride))
+            if (const char *why = check_frame_geometry(in.geo, fcols, frows, pf, in.stride))
                 throw std::runtime_error(std::string("Image geometry is not supported: ") + why);
-        } else if (in.by_format && (!in.pixels || (long long)in.stride < (long long)fcols * pf.bpp)) {
+        } else if (in.by_format && (!in.pixels || (long long)in.stride < pf.row_bytes(fcols))) {
             throw std::runtime_error("Image format is not supported: null pixels or stride < width * bytes per pixel");
         }
         // the upload that takes the frame: SCALED and FORMAT carry format / bits / limited_range, COLOR carries the channels
-        enum { GRAY, COLOR, FORMAT, SCALED } how = in.geo ? SCALED : pf.bpp == 2 || pf.rgb || pf.limited || pf.bayer ? FORMAT : pf.bpp != 1 ? COLOR : GRAY;
+        enum { GRAY, COLOR, FORMAT, SCALED } how = in.geo ? SCALED : pf.bpp == 2 || pf.rgb || pf.limited || pf.bayer || pf.packing ? FORMAT : pf.bpp != 1 ? COLOR : GRAY;
         const uint8_t *pixels = in.pixels;
         int stride = in.stride;
         if ((how == SCALED ? !have_scaled_upload() : how == FORMAT ? !have_format_upload() : how == COLOR && !have_color_upload()) || host_turn) {
             if (how == SCALED && in.on_device) throw std::runtime_error("Image geometry is not supported: this library cannot scale a frame in device memory");
-            if (host_turn && (!pixels || (how != SCALED && (long long)stride < (long long)fcols * pf.bpp))) throw std::runtime_error("Image is not supported: null pixels or stride < width * bytes per pixel");
+            if (host_turn && (!pixels || (how != SCALED && (long long)stride < pf.row_bytes(fcols)))) throw std::runtime_error("Image is not supported: null pixels or stride < width * bytes per pixel");
             gray_scratch.resize((size_t)cols * rows);
-            if (how == SCALED)
-                scale_frame(gray_scratch.data(), fcols, frows, crop_origin(pixels, stride, *in.geo, pf.bpp), stride, in.geo->crop_width, in.geo->crop_height,
-                            crop_pixel_format(pf, *in.geo));
+            if (how == SCALED) {
+                int x0 = 0;   // (a packed format: the crop's first column in the rows that crop_rows returns)
+                const uint8_t *crop = crop_rows(pixels, stride, *in.geo, pf, x0);
+                scale_frame(gray_scratch.data(), fcols, frows, crop, stride, in.geo->crop_width, in.geo->crop_height, crop_pixel_format(pf, *in.geo), x0);
+            }
             else reduce_frame(gray_scratch.data(), pixels, stride, fcols, frows, pf);   // BGR(A): cv::cvtColor BGR(A)2GRAY, (B*1868 + G*9617 + R*4899 + 8192) >> 14
             if (host_turn) {   // (scaling commutes with the orientations: the working-size plane is turned)
                 turn_scratch.resize(gray_scratch.size());

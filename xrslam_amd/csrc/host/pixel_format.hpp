@@ -9,6 +9,9 @@
 //   limited range (not for the 3 / 4 byte formats) gray' = min(255, ((max(gray, 16) - 16) * 255 + 109) / 219)
 //   Bayer mosaics (BAYER_*8 / *16: 1 / 2 bytes)    the sample s is the 1 / 2-byte value above (GRAY16's rule for *16); the gray value
 //                                                  needs the pixel's neighbours: bayer_gray below, a whole frame at a time
+//   packed 10 / 12 bits (GRAY*_MIPI, GRAY*P and     a row is bit-packed samples (packed_sample below: CSI-2 RAW10 / RAW12, PFNC lsb-packed); the
+//   their BAYER_* forms)                            sample then counts as GRAY16's / BAYER_*16's with bits = 10 / 12.  No byte address for a pixel:
+//                                                  samples are addressed by (row, x)
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -29,6 +32,19 @@ struct PixelFormat {
     bool limited = false;
     bool bayer = false;       // a colour-filter mosaic of 1 / 2-byte samples: the gray value is bayer_gray's, not reduce_pixel's
     int px = 0, py = 0;       // its pattern as a phase of RGGB: the colour site of (x, y) is RGGB's at ((x + px) & 1, (y + py) & 1)
+    // bit-packed samples (bpp is 0 then): PACK_MIPI: groups of whole pixels with their low bits in the group's last byte (10 bits: 4 px
+    // in 5 bytes; 12 bits: 2 px in 3); PACK_LSB: the row is one little-endian bit stream of `bits`-bit samples
+    enum Packing { PACK_NONE = 0, PACK_MIPI, PACK_LSB };
+    Packing packing = PACK_NONE;
+    int bits = 0;             // of a packed sample: 10 or 12
+    int group_px() const { return bits == 10 ? 4 : 2; }      // both packings start a byte every group_px pixels, group_bytes on
+    int group_bytes() const { return bits == 10 ? 5 : 3; }
+    // bytes that hold the first n pixels of a row
+    long long row_bytes(long long n) const {
+        if (packing == PACK_NONE) return n * bpp;
+        if (packing == PACK_MIPI) return (n + group_px() - 1) / group_px() * group_bytes();
+        return (n * bits + 7) / 8;
+    }
 };
 
 // nullptr, or which argument is wrong and why (the callers put their own name in front)
@@ -60,7 +76,22 @@ inline const char *describe_pixel_format(int format, int bits, int limited_range
             }
             break;
         }
-        default: return "format is not one of XRHIP_PIXFMT_*";
+        default: {
+            const bool mono = format >= XRHIP_PIXFMT_GRAY10_MIPI && format <= XRHIP_PIXFMT_GRAY12P;
+            if (!mono && !(format >= XRHIP_PIXFMT_BAYER_RGGB10_MIPI && format <= XRHIP_PIXFMT_BAYER_BGGR12P)) return "format is not one of XRHIP_PIXFMT_*";
+            // GRAY: 32 + packing; BAYER: 40 + 4 * packing + pattern; packing: 10_MIPI, 12_MIPI, 10P, 12P.  `bits` is not read.
+            const int packing = mono ? format - XRHIP_PIXFMT_GRAY10_MIPI : (format - XRHIP_PIXFMT_BAYER_RGGB10_MIPI) >> 2;
+            f.bpp = 0;
+            f.packing = packing < 2 ? PixelFormat::PACK_MIPI : PixelFormat::PACK_LSB;
+            f.bits = (packing & 1) ? 12 : 10;
+            f.shift = (uint32_t)(f.bits - 8);   // the sample is reduced like GRAY16 with bits = 10 / 12
+            if (!mono) {
+                const int pattern = (format - XRHIP_PIXFMT_BAYER_RGGB10_MIPI) & 3;
+                f.bayer = true;
+                f.px = pattern & 1;
+                f.py = pattern >> 1;
+            }
+        }
     }
     if (limited_range && f.bpp >= 3) return "limited_range does not apply to the RGB / BGR formats";
     if (limited_range && f.bayer) return "limited_range does not apply to the Bayer formats";
@@ -82,15 +113,32 @@ inline uint8_t reduce_pixel(const uint8_t *p, const PixelFormat &f) {
     return f.limited ? expand_limited_range(g) : (uint8_t)g;
 }
 
+// Sample x of the packed row at `row` (xrslam_hip.h has the table): reads the bytes that hold its bits and nothing else
+inline uint32_t packed_sample(const uint8_t *row, size_t x, const PixelFormat &f) {
+    if (f.packing == PixelFormat::PACK_MIPI) {
+        if (f.bits == 10) return (uint32_t)row[5 * (x >> 2) + (x & 3)] << 2 | ((uint32_t)row[5 * (x >> 2) + 4] >> (2 * (x & 3)) & 3u);
+        return (uint32_t)row[3 * (x >> 1) + (x & 1)] << 4 | ((uint32_t)row[3 * (x >> 1) + 2] >> (4 * (x & 1)) & 15u);
+    }
+    const size_t bit = x * (size_t)f.bits, b = bit >> 3;   // (bit & 7) + bits <= 16: two bytes
+    return (((uint32_t)row[b] | (uint32_t)row[b + 1] << 8) >> (bit & 7)) & ((1u << f.bits) - 1u);
+}
+// Pixel x of the row at `row`, of any format: reduce_pixel, or the packed sample reduced like GRAY16's
+inline uint8_t row_pixel(const uint8_t *row, size_t x, const PixelFormat &f) {
+    if (f.packing == PixelFormat::PACK_NONE) return reduce_pixel(row + x * (size_t)f.bpp, f);
+    const uint32_t g = std::min<uint32_t>(255u, packed_sample(row, x, f) >> f.shift);
+    return f.limited ? expand_limited_range(g) : (uint8_t)g;
+}
+
 // ------------------------------------------------------------------------------------------------ Bayer mosaics
 // Bilinear demosaicing followed by the BGR weights, in exact integer arithmetic with one rounding (xrslam_hip.h has the definition;
 // the device kernel k_upload_bayer and the numpy model tests/bayer_model.py give the same bits).  The frame is n_x x n_y samples;
 // neighbours outside it mirror without repeating the edge (-1 -> 1, n -> n - 2), which keeps every neighbour on a site of the colour
 // it stands for; n_x, n_y >= 2.  Every sum is four times the bilinear estimate; the weights sum to 16384.
 inline int bayer_mirror(int i, int n) { return i < 0 ? -i : i >= n ? 2 * n - 2 - i : i; }
-inline uint8_t bayer_gray(const uint8_t *src, long long stride, int n_x, int n_y, int x, int y, const PixelFormat &f) {
+// (x0: the frame's first column in the rows at `src`, for a crop of a packed frame)
+inline uint8_t bayer_gray(const uint8_t *src, long long stride, int n_x, int n_y, int x, int y, const PixelFormat &f, int x0 = 0) {
     const int xl = bayer_mirror(x - 1, n_x), xr = bayer_mirror(x + 1, n_x), yu = bayer_mirror(y - 1, n_y), yd = bayer_mirror(y + 1, n_y);
-    const auto s = [&](int xx, int yy) -> uint32_t { return reduce_pixel(src + (size_t)yy * (size_t)stride + (size_t)xx * f.bpp, f); };
+    const auto s = [&](int xx, int yy) -> uint32_t { return row_pixel(src + (size_t)yy * (size_t)stride, (size_t)x0 + (size_t)xx, f); };
     const uint32_t C = 4 * s(x, y), Hh = 2 * (s(xl, y) + s(xr, y)), Vv = 2 * (s(x, yu) + s(x, yd)), P = (Hh + Vv) / 2;
     const uint32_t X = s(xl, yu) + s(xr, yu) + s(xl, yd) + s(xr, yd);
     const int cx = (x + f.px) & 1, cy = (y + f.py) & 1;   // RGGB's site: (0,0) red, (1,1) blue, (1,0) green between reds, (0,1) between blues
@@ -116,17 +164,18 @@ inline PixelFormat crop_pixel_format(PixelFormat f, const xrhip_frame_geometry &
 }
 
 // `rows` rows of `cols` pixels at `src` (rows `stride` bytes apart, any alignment) into the dense gray plane `dst`: reads
-// cols * f.bpp bytes of each of the rows and nothing else
-inline void reduce_frame(uint8_t *dst, const uint8_t *src, int stride, int cols, int rows, const PixelFormat &f) {
+// cols * f.bpp bytes of each of the rows and nothing else.  A packed format: the pixels are columns x0 .. x0 + cols - 1 of the rows
+// that start at `src`, and the bytes that hold their samples are read.
+inline void reduce_frame(uint8_t *dst, const uint8_t *src, int stride, int cols, int rows, const PixelFormat &f, int x0 = 0) {
     if (f.bayer) {
         for (int y = 0; y < rows; ++y)
-            for (int x = 0; x < cols; ++x) dst[(size_t)y * cols + x] = bayer_gray(src, stride, cols, rows, x, y, f);
+            for (int x = 0; x < cols; ++x) dst[(size_t)y * cols + x] = bayer_gray(src, stride, cols, rows, x, y, f, x0);
         return;
     }
     for (int y = 0; y < rows; ++y) {
         const uint8_t *s = src + (size_t)y * stride;
         uint8_t *d = dst + (size_t)y * cols;
-        for (int x = 0; x < cols; ++x) d[x] = reduce_pixel(s + (size_t)x * f.bpp, f);
+        for (int x = 0; x < cols; ++x) d[x] = row_pixel(s, (size_t)x0 + (size_t)x, f);
     }
 }
 
@@ -158,19 +207,38 @@ inline const char *check_frame_geometry(const xrhip_frame_geometry *g, int W, in
     if (stride < (long long)g->src_width * bpp) return "stride_bytes < src_width * bytes per pixel";
     return nullptr;
 }
+// the same for any format: the stride holds the (packed) bytes of a source row
+inline const char *check_frame_geometry(const xrhip_frame_geometry *g, int W, int H, const PixelFormat &f, long long stride) {
+    if (f.packing == PixelFormat::PACK_NONE) return check_frame_geometry(g, W, H, f.bpp, stride);
+    const char *why = check_frame_geometry(g, W, H, 0, stride);
+    if (!why && stride < f.row_bytes(g->src_width)) why = "stride_bytes < the packed bytes of a row of src_width pixels";
+    return why;
+}
 
 // The crop's first byte in a frame whose row 0 starts at `pixels`
 inline const uint8_t *crop_origin(const uint8_t *pixels, long long stride, const xrhip_frame_geometry &g, int bpp) {
     return pixels + (size_t)g.crop_y * (size_t)stride + (size_t)g.crop_x * bpp;
 }
+// The same for any format, as (rows, x0): a packed pixel has no byte address, so the crop is columns x0 .. of the rows that start at
+// the returned byte -- the byte at which the group of crop_x starts (both packings start a byte every group_px pixels), x0 the
+// crop's first column counted from there.  Other formats: crop_origin and x0 = 0.
+inline const uint8_t *crop_rows(const uint8_t *pixels, long long stride, const xrhip_frame_geometry &g, const PixelFormat &f, int &x0) {
+    if (f.packing == PixelFormat::PACK_NONE) {
+        x0 = 0;
+        return crop_origin(pixels, stride, g, f.bpp);
+    }
+    x0 = g.crop_x % f.group_px();
+    return pixels + (size_t)g.crop_y * (size_t)stride + (size_t)(g.crop_x / f.group_px()) * (size_t)f.group_bytes();
+}
 
 // `src`: the crop's first byte (rows `stride` bytes apart, cw x ch pixels of f.bpp bytes) -> the dense W x H plane `dst`.  Reads the
 // cw * f.bpp bytes of each of the ch rows and nothing else.  A Bayer crop (f: crop_pixel_format) is a Bayer frame of its own: it is
-// demosaiced whole, its neighbours mirrored at the crop's edges, and the gray crop is scaled.
-inline void scale_frame(uint8_t *dst, int W, int H, const uint8_t *src, long long stride, int cw, int ch, const PixelFormat &f) {
+// demosaiced whole, its neighbours mirrored at the crop's edges, and the gray crop is scaled.  A packed format: (src, col0) are
+// crop_rows', and the bytes that hold the crop's samples are read.
+inline void scale_frame(uint8_t *dst, int W, int H, const uint8_t *src, long long stride, int cw, int ch, const PixelFormat &f, int col0 = 0) {
     if (f.bayer) {
         std::vector<uint8_t> gray((size_t)cw * ch);
-        reduce_frame(gray.data(), src, (int)stride, cw, ch, f);
+        reduce_frame(gray.data(), src, (int)stride, cw, ch, f, col0);
         return scale_frame(dst, W, H, gray.data(), cw, cw, ch, PixelFormat());
     }
     const uint32_t area = (uint32_t)cw * (uint32_t)ch, half = area / 2;
@@ -187,7 +255,7 @@ inline void scale_frame(uint8_t *dst, int W, int H, const uint8_t *src, long lon
                 uint32_t r = 0;
                 for (int i = i0; i < i1; ++i) {
                     const uint32_t a = (uint32_t)(std::min<long long>((long long)(i + 1) * W, x1) - std::max<long long>((long long)i * W, x0));
-                    r += a * reduce_pixel(row + (size_t)i * f.bpp, f);
+                    r += a * row_pixel(row, (size_t)col0 + (size_t)i, f);
                 }
                 acc += b * r;
             }

@@ -136,7 +136,8 @@ struct xrhip_klt {
     double view_ms = 0;
     long long view_n = 0;
     // frames larger than the plane (xrhip_image_upload_scaled): the crop of a host frame in HBM, where k_upload_scaled reads it.
-    // Nothing of it exists before the first scaled (or Bayer) upload of a host frame.
+    // Nothing of it exists before the first scaled (or Bayer) upload of a host frame.  A packed mosaic or scaled packed frame (host
+    // or HBM) has its 8-bit samples unpacked into it (upload_packed_into).
     uint8_t *scale_src = nullptr;
     size_t scale_cap = 0;
     // Bayer mosaics (XRHIP_PIXFMT_BAYER_*): a host mosaic is staged in scale_src as well (k_upload_bayer reads it there); a scaled one
@@ -733,9 +734,10 @@ static int check_frame(const char *who, const xrhip_image *im, const FrameSource
     if (!s.pixels) return frame_fail(XRHIP_EINVAL, who, "pixels is null");
     if (bad_format) return frame_fail(XRHIP_EINVAL, who, bad_format);
     if (s.scaled) {
-        if (const char *why = xrh::check_frame_geometry(s.geo, s.pw, s.ph, s.pf.bpp, s.stride))
+        if (const char *why = xrh::check_frame_geometry(s.geo, s.pw, s.ph, s.pf, s.stride))
             return frame_fail(XRHIP_EINVAL, who, s.pw == im->ctx->w ? why : (std::string(why) + " (orientation: the frame is turned, the crop must cover height x width)").c_str());
-    } else if ((long long)s.stride < (long long)s.pw * s.pf.bpp) {
+    } else if ((long long)s.stride < s.pf.row_bytes(s.pw)) {
+        if (s.pf.packing) return frame_fail(XRHIP_EINVAL, who, "stride_bytes < the packed bytes of a row");
         return frame_fail(XRHIP_EINVAL, who, s.pw == im->ctx->w ? "stride_bytes < width * bytes per pixel"
                                                                  : "stride_bytes < height * bytes per pixel (orientation: the frame is height x width in memory)");
     }
@@ -970,6 +972,79 @@ static int upload_bayer_into(xrhip_klt *c, const FrameSource &s, uint8_t *dst) {
     return slot_in_flight(c, slot);
 }
 
+// Packed 10 / 12-bit samples (XRHIP_PIXFMT_*_MIPI, *10P, *12P), unpacked by k_upload_packed: launches of their own in the context's
+// order, like the Bayer upload (a group member: on the group's front-end queue, behind a pending upload, which is submitted first).
+//   a mono frame of the plane's size   k_upload_packed -> the plane                                                    1 launch
+//   a scaled mono frame                k_upload_packed -> the crop's 8-bit samples in scale_src; k_upload_scaled       2
+//   a mosaic                           k_upload_packed -> its 8-bit samples in scale_src; k_upload_bayer               2
+//   a scaled mosaic                    ... k_upload_bayer -> bayer_gray; k_upload_scaled                               3
+// Exact: the Bayer and scaled definitions reduce a sample to 8 bits before anything else.  Only the byte groups that hold a pixel of
+// the frame (scaled: of the crop) are read.  A host frame: those bytes, packed, go through the pinned slot, which the kernel reads
+// mapped -- every sample is unpacked by one lane, so its bytes cross the host link once (a dword at the seam of two lanes' runs may be
+// fetched by both, as in k_upload), at 1.25 / 1.5 bytes a pixel.
+static int upload_packed_into(xrhip_klt *c, const FrameSource &s, uint8_t *dst) {
+    const xrh::PixelFormat pf = s.scaled ? xrh::crop_pixel_format(s.pf, *s.geo) : s.pf;
+    const int rw = s.scaled ? s.geo->crop_width : s.pw, rh = s.scaled ? s.geo->crop_height : s.ph;
+    const xrhip_frame_geometry whole{s.pw, s.ph, 0, 0, s.pw, s.ph};
+    PackedArgs a{};
+    a.src = xrh::crop_rows(s.pixels, s.stride, s.scaled ? *s.geo : whole, pf, a.x0);
+    a.sstride = s.stride;
+    a.dst = dst;
+    a.w = rw;
+    a.h = rh;
+    a.bits = pf.bits;
+    a.mipi = pf.packing == xrh::PixelFormat::PACK_MIPI;
+    a.limited = pf.limited;
+    const size_t pixels = (size_t)rw * rh;
+    const bool scaled = s.scaled, bayer = pf.bayer;
+    int rc = XRHIP_OK;
+    if (scaled || bayer) {   // the 8-bit samples, for the kernels that follow
+        rc = grow_scratch(c, c->scale_src, c->scale_cap, (pixels + 3) & ~(size_t)3);
+        if (rc) return rc;
+        a.dst = c->scale_src;
+    }
+    if (scaled && bayer) {
+        rc = grow_scratch(c, c->bayer_gray, c->bayer_gray_cap, pixels);
+        if (rc) return rc;
+    }
+    BayerArgs ba{};
+    ba.src = c->scale_src;
+    ba.sstride = rw;
+    ba.dst = scaled ? c->bayer_gray : dst;
+    ba.w = rw;
+    ba.h = rh;
+    ba.bpp = 1;
+    ba.px = pf.px;
+    ba.py = pf.py;
+    const ScaleArgs sa = scale_args(s.pw, s.ph, bayer ? c->bayer_gray : c->scale_src, rw, 1, 0, rw, rh, dst);   // (scaled only)
+    const dim3 grid = grid_of_fours(pixels), scale_grid = grid_of_fours((size_t)s.pw * s.ph);
+    int slot = -1;
+    if (!s.on_device) {
+        const size_t row = (size_t)pf.row_bytes((long long)a.x0 + rw);
+        rc = slot_fill(c, a.src, s.stride, row, rh, slot);
+        if (rc) return rc;
+        uint8_t *dbuf = nullptr;
+        XR_HIP(hipHostGetDevicePointer((void **)&dbuf, c->up_buf[slot], 0));
+        a.src = dbuf;
+        a.sstride = (int)row;
+    }
+    rc = klt_run(c, [=](hipStream_t st) {
+        hipLaunchKernelGGL(k_upload_packed, grid, dim3(256), 0, st, a);
+        XR_HIP(hipGetLastError());
+        if (bayer) {
+            hipLaunchKernelGGL(k_upload_bayer, grid, dim3(256), 0, st, ba);
+            XR_HIP(hipGetLastError());
+        }
+        if (scaled) {
+            hipLaunchKernelGGL(k_upload_scaled, scale_grid, dim3(256), 0, st, sa);
+            XR_HIP(hipGetLastError());
+        }
+        return XRHIP_OK;
+    });
+    if (rc || slot < 0) return rc;
+    return slot_in_flight(c, slot);
+}
+
 // Every xrhip_image_upload* entry point (`who`).  distorted: the frame is as the camera recorded it and k_undistort rectifies it into
 // the plane -- reduced / scaled into undist_src first, rectified second: the gray frame takes the place of the one a gray camera of
 // the plane's size would have recorded; such a frame already in HBM is remapped where it lies.
@@ -991,7 +1066,7 @@ static int upload_frame(xrhip_image *im, const FrameSource &handed, const char *
     if (distorted && !c->have_undist) return frame_fail(XRHIP_ESTATE, who, "no undistortion map (xrhip_klt_set_undistort_map)");
     const uint8_t *remap_src = c->undist_src;
     int remap_stride = c->w;
-    if (o == 0 && distorted && s.on_device && !s.scaled && !s.pf.bayer && s.pf.bpp == 1 && upf_word(s.pf) == 0) {
+    if (o == 0 && distorted && s.on_device && !s.scaled && !s.pf.bayer && !s.pf.packing && s.pf.bpp == 1 && upf_word(s.pf) == 0) {
         remap_src = s.pixels;
         remap_stride = s.stride;
     } else {
@@ -1003,7 +1078,8 @@ static int upload_frame(xrhip_image *im, const FrameSource &handed, const char *
             if (!c->orient_src) XR_HIP(hipMalloc(&c->orient_src, ((size_t)c->w * c->h + 3) & ~(size_t)3));
             dst = c->orient_src;
         }
-        rc = s.pf.bayer ? upload_bayer_into(c, s, dst) : s.scaled ? upload_scaled_into(c, s, dst) : upload_into(c, s, dst);
+        rc = s.pf.packing ? upload_packed_into(c, s, dst)
+             : s.pf.bayer ? upload_bayer_into(c, s, dst) : s.scaled ? upload_scaled_into(c, s, dst) : upload_into(c, s, dst);
         if (rc) return rc;
         if (o != 0) {
             // in source coordinates: r even: (fx ? w-1-X : X, fy ? h-1-Y : Y); r odd: (fx ? h-1-Y : Y, fy ? w-1-X : X)

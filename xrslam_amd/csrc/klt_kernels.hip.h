@@ -1880,6 +1880,88 @@ __global__ __launch_bounds__(256) void k_upload_bayer(BayerArgs a) {
     d_upload_bayer<1>(a);
 }
 
+// ------------------------------------------------------------------------------- packed 10 / 12-bit samples (XRHIP_PIXFMT_*_MIPI, *10P, *12P)
+// Rows of bit-packed samples (xrslam_hip.h has the table; host/pixel_format.hpp: packed_sample is the definition in C++) unpacked to
+// a dense w x h plane of 8-bit values: plane pixel (X, Y) is min(255, v >> (bits - 8)) of sample x0 + X of the row at
+// src + Y * sstride -- the sample's top 8 bits, so the MIPI forms never read a group's low-bits byte for it.  A mono frame of the
+// plane's size goes straight to the gray plane (`limited` expands video levels); a mosaic or a scaled frame goes to an HBM scratch
+// from which k_upload_bayer / k_upload_scaled take it at one byte a sample (their definitions reduce a sample to 8 bits first).
+// x0: a crop's first column in its rows (a row address is a byte address; a packed pixel has none).
+struct PackedArgs {
+    const uint8_t *src;
+    int sstride;
+    uint8_t *dst;   // dense w x h, dword aligned
+    int w, h;
+    int x0;
+    int bits;       // 10 or 12
+    int mipi;       // 1: CSI-2 groups (4 px in 5 bytes / 2 in 3); 0: the row is one little-endian bit stream
+    int limited;
+};
+// The bit of the row at which the top 8 bits of sample x start.  MIPI: its own byte, x + x / 4 (10) or x + x / 2 (12).
+__device__ __forceinline__ uint64_t packed_top_bit(uint32_t x, uint32_t bits, bool mipi) {
+    if (mipi) return 8ull * ((uint64_t)x + (x >> (bits == 10u ? 2 : 1)));
+    return (uint64_t)x * bits + (bits - 8u);
+}
+// The `n` bytes (1..8) from byte address `ad` on (any alignment), low byte first, out of the aligned dwords that cover exactly them:
+// the first holds byte 0 and the last byte n - 1, so a caller whose first and last bytes are needed ones fetches no stray dword.
+// (load_dwords_unaligned<2> would fetch a third dword whenever ad is unaligned, also where the n < 8 bytes end before it.)
+__device__ __forceinline__ uint64_t load_bytes_unaligned(uintptr_t ad, uint32_t n) {
+    const uint32_t *q = reinterpret_cast<const uint32_t *>(ad & ~(uintptr_t)3);
+    const uint32_t off = (uint32_t)(ad & 3), last = (off + n - 1u) >> 2;   // 0..2
+    uint32_t d0 = q[0], d1 = 0, d2 = 0;
+    if (last >= 1u) d1 = q[1];
+    if (last >= 2u) d2 = q[2];
+    if (off) {
+        const uint32_t sh = off * 8u;
+        d0 = (d0 >> sh) | (d1 << (32u - sh));
+        d1 = (d1 >> sh) | (d2 << (32u - sh));
+    }
+    return (uint64_t)d0 | ((uint64_t)d1 << 32);
+}
+// one pixel, byte by byte: the one or two bytes that hold its top 8 bits
+__device__ __forceinline__ uint32_t packed_gray1(const uint8_t *row, uint32_t x, uint32_t bits, bool mipi, bool limited) {
+    const uint64_t bit = packed_top_bit(x, bits, mipi);
+    const uint8_t *p = row + (size_t)(bit >> 3);
+    const uint32_t sh = (uint32_t)bit & 7u;
+    const uint32_t v = sh ? ((uint32_t)p[0] | ((uint32_t)p[1] << 8)) >> sh : (uint32_t)p[0];
+    return narrow_to_gray(v, 0xffu, 0u, limited);
+}
+// A lane owns four consecutive plane pixels = one dword store, as in d_upload_reduce.  Where the four lie in one row it fetches the
+// aligned dwords that cover the bytes from the one that holds the first bit of the first pixel's top 8 bits to the one that holds the
+// last bit of the fourth's: 4 bytes (MIPI10 at x % 4 == 0: the four gray values are those bytes), else 5 or 6 -- the bit phase
+// (bits * x) & 7 is non-zero whenever x is not a multiple of 4, which w % 4 != 0 or a crop brings about in every row.  The first and
+// the last of these bytes are needed and all between them are bytes of the row, so every fetched aligned dword holds at least one
+// needed byte and nothing outside the frame's pages is touched (load_bytes_unaligned is given the byte count: 6 bytes reach a third
+// dword only from offset 3).  Groups of four that straddle a plane row end (w % 4 != 0) and the plane's tail go byte by byte.
+__global__ __launch_bounds__(256) void k_upload_packed(PackedArgs a) {
+    const uint32_t w = (uint32_t)a.w, total = w * (uint32_t)a.h, bits = (uint32_t)a.bits;
+    const uint32_t n4 = (total + 3u) >> 2;
+    const bool mipi = a.mipi != 0, limited = a.limited != 0;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n4; i += gridDim.x * 256u) {
+        const uint32_t p0 = i << 2;
+        const uint32_t y = p0 / w, x = p0 - y * w;
+        if (x + 4u <= w) {   // (p0 + 4 <= total follows)
+            const uint32_t xs = (uint32_t)a.x0 + x;
+            uint64_t t[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) t[k] = packed_top_bit(xs + (uint32_t)k, bits, mipi);
+            const uint64_t first = t[0] >> 3, lastb = (t[3] + 7u) >> 3;   // bytes of the row
+            const uint64_t v = load_bytes_unaligned(reinterpret_cast<uintptr_t>(a.src + (size_t)y * (size_t)a.sstride + (size_t)first),
+                                                    (uint32_t)(lastb - first) + 1u);
+            uint32_t g[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g[k] = narrow_to_gray((uint32_t)(v >> (uint32_t)(t[k] - 8u * first)), 0xffu, 0u, limited);
+            reinterpret_cast<uint32_t *>(a.dst)[i] = g[0] | (g[1] << 8) | (g[2] << 16) | (g[3] << 24);
+        } else {
+            const uint32_t pe = p0 + 4u < total ? p0 + 4u : total;
+            for (uint32_t p = p0; p < pe; ++p) {
+                const uint32_t py = p / w;
+                a.dst[p] = (uint8_t)packed_gray1(a.src + (size_t)py * (size_t)a.sstride, (uint32_t)a.x0 + (p - py * w), bits, mipi, limited);
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------- turned and mirrored frames (xrhip_klt_set_orientation)
 // The dense gray plane of a frame in the source's orientation -> the dense w x h plane, for the seven orientations o = r + 4 f other
 // than 0 (xrslam_hip.h has the definition).  In source coordinates the plane pixel (X, Y) is

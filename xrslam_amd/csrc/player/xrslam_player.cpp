@@ -7,7 +7,8 @@
 //
 //   xrslam-player --slam configs/euroc_slam.yaml --device configs/euroc_sensor.yaml --euroc <dir>/mav0
 //                 [--out traj.tum] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined]
-//                 [--push-color] [--push-format gray16|rgb|rgba|bayer_rggb8|bayer_bggr16] [--push-scaled] [--cov-out FILE]
+//                 [--push-color] [--push-format gray16|rgb|rgba|bayer_rggb8|bayer_bggr16|gray10_mipi|gray12_mipi|gray10p|gray12p|
+//                  bayer_rggb10_mipi|bayer_bggr12p] [--push-scaled] [--cov-out FILE]
 //                 [--push-oriented rot90|rot180|rot270|flip|flip-rot90|flip-rot180|flip-rot270|0..7]
 //
 // (--push-color: a colour PNG is pushed as BGR / BGRA with channel 3 / 4 and reduced to gray by the library instead of by the reader.)
@@ -18,7 +19,9 @@
 // Works through --push-color / --push-format / --push-scaled; the reader's own rectification (--host-undistort) takes upright frames.)
 // (--push-format: a 16-bit PNG is handed to the library as GRAY16 instead of being stripped to its high byte by the reader; a colour
 // PNG as RGB8 / RGBA8 -- XRSLAMAmdPushImageFormat.  bayer_rggb8 / bayer_bggr16: the gray PNG becomes a raw mosaic whose every site
-// holds the gray value -- bytes, or 16-bit samples with the value in the high byte -- and is pushed as BAYER_RGGB8 / BAYER_BGGR16.)
+// holds the gray value -- bytes, or 16-bit samples with the value in the high byte -- and is pushed as BAYER_RGGB8 / BAYER_BGGR16.
+// gray10_mipi .. bayer_bggr12p: the gray PNG -- a 16-bit one keeps its top 10 / 12 bits, an 8-bit one is shifted up -- is re-packed into
+// the CSI-2 RAW10 / RAW12 or PFNC lsb-packed rows a sensor would send and pushed as that format, after any --push-oriented turn.)
 // (--pipelined: XRSLAMAmdSetThreading(1), the reference's XRSLAM_ENABLE_THREADING build with deterministic hand-offs.)
 // The reference player's own command line (main.cpp:57-79) is accepted as well, so its invocations carry over:
 //
@@ -77,6 +80,33 @@ static void turn_back(GrayImage &img, int o) {
     img.h = H;
 }
 
+// --push-format <packed>: the frame's samples (16-bit PNG: little-endian pairs, else bytes; the top pf.bits bits are kept) packed into
+// dense rows of pf's packing (include/XRSLAM.h has the layouts), the frame a sensor would send.  -> the row's bytes
+static int pack_image(GrayImage &img, const xrh::PixelFormat &pf) {
+    const int row = (int)pf.row_bytes(img.w), low = pf.bits - 8, c = img.channels;
+    std::vector<uint8_t> out((size_t)row * img.h, 0);
+    for (int y = 0; y < img.h; ++y) {
+        uint8_t *B = &out[(size_t)y * row];
+        for (int x = 0; x < img.w; ++x) {
+            const uint8_t *p = &img.px[((size_t)y * img.w + x) * c];
+            const uint32_t v16 = c == 2 ? (uint32_t)p[0] | (uint32_t)p[1] << 8 : (uint32_t)p[0] << 8, v = v16 >> (16 - pf.bits);
+            if (pf.packing == xrh::PixelFormat::PACK_MIPI) {
+                const int g = x / pf.group_px(), i = x % pf.group_px();
+                B[g * pf.group_bytes() + i] = (uint8_t)(v >> low);
+                B[g * pf.group_bytes() + pf.group_px()] |= (uint8_t)((v & ((1u << low) - 1u)) << (low * i));
+            } else {
+                const size_t bit = (size_t)x * pf.bits;
+                const uint32_t s = v << (bit & 7);
+                B[bit >> 3] |= (uint8_t)s;
+                B[(bit >> 3) + 1] |= (uint8_t)(s >> 8);
+            }
+        }
+    }
+    img.px.swap(out);
+    img.channels = 0;   // (no whole bytes per pixel)
+    return row;
+}
+
 static const TruthRow *nearest_truth(const std::vector<TruthRow> &gt, double t, double tol) {
     if (gt.empty()) return nullptr;
     size_t lo = 0, hi = gt.size();
@@ -95,6 +125,7 @@ int main(int argc, char **argv) {
     bool undistort = true, host_undistort = false, pipelined = false, push_color = false, push_scaled = false;
     int png_keep = PNG_GRAY;   // --push-format
     int push_bayer = -1;       // --push-format bayer_*: the XRSLAMAmdPixelFormat the gray frames are pushed as
+    int push_packed = -1;      // --push-format gray10_mipi ...: the packed XRSLAMAmdPixelFormat the gray frames are re-packed to
     int push_oriented = 0;     // --push-oriented: the orientation the frames are pushed in
     // the reference's option names (main.cpp:57-71) map onto ours
     const std::map<std::string, std::string> alias = {{"-sc", "slam"}, {"--slamconfig", "slam"}, {"-dc", "device"},
@@ -121,10 +152,18 @@ int main(int argc, char **argv) {
             else if (f == "rgba") png_keep = PNG_KEEP_RGBA;
             else if (f == "bayer_rggb8") push_bayer = XRSLAM_AMD_PIXEL_BAYER_RGGB8;
             else if (f == "bayer_bggr16") push_bayer = XRSLAM_AMD_PIXEL_BAYER_BGGR16;
+            else if (f == "gray10_mipi") push_packed = XRSLAM_AMD_PIXEL_GRAY10_MIPI;
+            else if (f == "gray12_mipi") push_packed = XRSLAM_AMD_PIXEL_GRAY12_MIPI;
+            else if (f == "gray10p") push_packed = XRSLAM_AMD_PIXEL_GRAY10P;
+            else if (f == "gray12p") push_packed = XRSLAM_AMD_PIXEL_GRAY12P;
+            else if (f == "bayer_rggb10_mipi") push_packed = XRSLAM_AMD_PIXEL_BAYER_RGGB10_MIPI;
+            else if (f == "bayer_bggr12p") push_packed = XRSLAM_AMD_PIXEL_BAYER_BGGR12P;
             else {
-                std::fprintf(stderr, "--push-format: gray16, rgb, rgba, bayer_rggb8 or bayer_bggr16\n");
+                std::fprintf(stderr, "--push-format: gray16, rgb, rgba, bayer_rggb8, bayer_bggr16, gray10_mipi, gray12_mipi, gray10p, gray12p, "
+                                     "bayer_rggb10_mipi or bayer_bggr12p\n");
                 return 2;
             }
+            if (push_packed >= 0) png_keep = PNG_KEEP_GRAY16;   // (a 16-bit PNG keeps its low byte for the packer)
         }
         else if (a == "-p" || a == "--play") continue;
         else if (alias.count(a) && i + 1 < argc) opt[alias.at(a)] = argv[++i];
@@ -147,7 +186,7 @@ int main(int argc, char **argv) {
     }
     if (!opt.count("slam") || !opt.count("device") || !opt.count("euroc")) {
         std::fprintf(stderr, "usage: xrslam-player --slam cfg.yaml --device sensor.yaml --euroc <dir>/mav0 [--out traj.tum] "
-                             "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color] [--push-format gray16|rgb|rgba|bayer_rggb8|bayer_bggr16] [--push-scaled] [--push-oriented rot90|rot180|rot270|flip|...|0..7] [--mask mask.pgm|mask.png]\n"
+                             "[--csv traj.csv] [--bootstrap-frames N] [--max-frames N] [--no-undistort | --host-undistort] [--pipelined] [--push-color] [--push-format gray16|rgb|rgba|bayer_rggb8|bayer_bggr16|gray10_mipi|gray12_mipi|gray10p|gray12p|bayer_rggb10_mipi|bayer_bggr12p] [--push-scaled] [--push-oriented rot90|rot180|rot270|flip|...|0..7] [--mask mask.pgm|mask.png]\n"
                              "       [--cov-out FILE] [--view-out DIR [--view-every N] [--view-mode reference|age] [--view-trail K]]\n"
                              "   or: xrslam-player -sc cfg.yaml -dc sensor.yaml [--tum traj.tum] [--csv traj.csv] [-p] "
                              "euroc://<dir>/mav0 | tum://<dir>/mav0\n");
@@ -313,6 +352,13 @@ int main(int argc, char **argv) {
                 }
                 turn_back(img, push_oriented);
             }
+            int stride = img.w * img.channels;
+            if (push_packed >= 0 && img.channels <= 2 && (img.pixel_format < 0 || img.pixel_format == XRSLAM_AMD_PIXEL_GRAY16)) {
+                xrh::PixelFormat pf;
+                xrh::describe_pixel_format(push_packed, 0, 0, pf);
+                stride = pack_image(img, pf);
+                img.pixel_format = push_packed;
+            }
             const bool oversized = push_scaled && img.w >= frame_w && img.h >= frame_h && (img.w != frame_w || img.h != frame_h);
             if (oversized) {   // --push-scaled: the frame goes in at its own size, the whole of it as the crop
                 if (undistort && cfg.cam_distortion_flag && !device_undistort) {
@@ -325,19 +371,19 @@ int main(int argc, char **argv) {
                                               : img.channels == 3 ? (int)XRSLAM_AMD_PIXEL_BGR8
                                               : img.channels == 4 ? (int)XRSLAM_AMD_PIXEL_BGRA8 : (int)XRSLAM_AMD_PIXEL_GRAY8, 0, 0};
                 const XRSLAMAmdFrameGeometry geo{img.w, img.h, 0, 0, img.w, img.h};
-                XRSLAMAmdPushImageScaled(img.px.data(), img.w * img.channels, &ff, &geo, 0, ev.t);
+                XRSLAMAmdPushImageScaled(img.px.data(), stride, &ff, &geo, 0, ev.t);
             } else if (img.w != frame_w || img.h != frame_h) {
                 std::fprintf(stderr, "%s: image is %dx%d, the device configuration says %dx%d\n", cam[ev.index].filename.c_str(), img.w,
                              img.h, frame_w, frame_h);
                 break;
             }
             const bool rectify_here = !oversized && undistort && cfg.cam_distortion_flag && !device_undistort;
-            const bool mosaic = img.pixel_format >= XRSLAM_AMD_PIXEL_BAYER_RGGB8;
+            const bool mosaic = img.pixel_format >= XRSLAM_AMD_PIXEL_BAYER_RGGB8;   // (or packed: reduce_frame's either way)
             if ((img.channels != 1 || mosaic) && rectify_here) {   // the host remap takes gray: reduced first, rectified second, as in the library
                 std::vector<uint8_t> g((size_t)img.w * img.h);
                 xrh::PixelFormat pf;
                 if (mosaic && !xrh::describe_pixel_format(img.pixel_format, 0, 0, pf))
-                    xrh::reduce_frame(g.data(), img.px.data(), img.w * img.channels, img.w, img.h, pf);
+                    xrh::reduce_frame(g.data(), img.px.data(), stride, img.w, img.h, pf);
                 for (size_t i = 0; i < g.size() && !mosaic; ++i) {
                     const uint8_t *c = &img.px[i * img.channels];
                     if (img.pixel_format == XRSLAM_AMD_PIXEL_GRAY16) g[i] = c[1];   // 16 significant bits: the high byte
@@ -363,7 +409,7 @@ int main(int argc, char **argv) {
                 // (pushed above)
             } else if (img.pixel_format >= 0) {
                 const XRSLAMAmdFrameFormat ff{img.pixel_format, 0, 0};
-                XRSLAMAmdPushImageFormat(pixels, img.w * img.channels, &ff, 0, ev.t);
+                XRSLAMAmdPushImageFormat(pixels, stride, &ff, 0, ev.t);
             } else {
                 XRSLAMImage xi;
                 std::memset(&xi, 0, sizeof(xi));

@@ -72,15 +72,20 @@ PIXEL_FORMATS = {name: i for i, name in enumerate(("gray8", "bgr8", "bgra8", "rg
                                                    "p010"))}
 PIXEL_FORMATS.update({name: 16 + i for i, name in enumerate(("bayer_rggb8", "bayer_grbg8", "bayer_gbrg8", "bayer_bggr8", "bayer_rggb16",
                                                              "bayer_grbg16", "bayer_gbrg16", "bayer_bggr16"))})   # (11..15 are not formats)
+# packed 10 / 12-bit samples, in a table of their own: gray* = 32 + packing, bayer_* = 40 + 4 * packing + pattern
+_PACKINGS = ("10_mipi", "12_mipi", "10p", "12p")
+PACKED_PIXEL_FORMATS = {"gray" + pk: 32 + p for p, pk in enumerate(_PACKINGS)}
+PACKED_PIXEL_FORMATS.update({"bayer_%s%s" % (pat, pk): 40 + 4 * p + k for p, pk in enumerate(_PACKINGS)
+                             for k, pat in enumerate(("rggb", "grbg", "gbrg", "bggr"))})
 
 
 def frame_format(pixel_format):
-    """'yuyv', ('gray16', 10), ('nv12', 0, 1), 'bayer_grbg8', ('bayer_rggb16', 12) or numbers in their place -> XRSLAMAmdFrameFormat (format, bits, limited_range)"""
+    """'yuyv', ('gray16', 10), ('nv12', 0, 1), 'bayer_grbg8', ('bayer_rggb16', 12), 'gray10_mipi' or numbers in their place -> XRSLAMAmdFrameFormat (format, bits, limited_range)"""
     if isinstance(pixel_format, XRSLAMAmdFrameFormat):
         return pixel_format
     f = tuple(pixel_format) if isinstance(pixel_format, (tuple, list)) else (pixel_format,)
     f = f + (0,) * (3 - len(f))
-    return XRSLAMAmdFrameFormat(PIXEL_FORMATS[f[0]] if isinstance(f[0], str) else int(f[0]), int(f[1]), int(f[2]))
+    return XRSLAMAmdFrameFormat((PIXEL_FORMATS[f[0]] if f[0] in PIXEL_FORMATS else PACKED_PIXEL_FORMATS[f[0]]) if isinstance(f[0], str) else int(f[0]), int(f[1]), int(f[2]))
 
 
 class XRSLAMAmdFrameGeometry(C.Structure):

@@ -271,7 +271,8 @@ class HipImage:
     def upload_format(self, pixels, fmt, bits=0, limited_range=0, on_device=False, stride=None):
         """A frame in one of the XRHIP_PIXFMT_* layouts (fmt: xrslam_amd.abi.PIXFMT_*, the Bayer mosaics PIXFMT_BAYER_* included), reduced
         to gray on its way in: a uint8 array of the frame's bytes, [h][row bytes] or [h][w][bytes per pixel] (rows may be strided), or
-        -- on_device -- a device pointer with its row stride in bytes."""
+        -- on_device -- a device pointer with its row stride in bytes.  The packed 10 / 12-bit formats (abi.PIXFMT_PACKED): [h][row
+        bytes], abi.packed_row_bytes(fmt, w) or more a row; `bits` is not read."""
         self._upload(L().xrhip_image_upload_format, pixels, on_device, stride, int(fmt), int(bits), int(limited_range), 1 if on_device else 0)
 
     def upload_format_distorted(self, pixels, fmt, bits=0, limited_range=0, on_device=False, stride=None):
